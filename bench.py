@@ -31,9 +31,21 @@ before the communicator exists): the same-job W=1 anchor.  The line then carries
 status, all-gathered; a repeated device or an RCCL communicator whose size is not N (the reference's
 every-rank-on-GPU-0 bug, /root/reference/mnist/main.py:181-182) fails the run with an error line.
 
-At W=1 the line also carries ``w1_rccl_comm``: the same step measured a second time with an RCCL
-communicator initialised and the full W>1 communication path running (config 2 of BASELINE.json:
-"DDP world_size=1 ... RCCL init + HIP kernels"); the headline ``value`` stays the comm-free step.
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the result line.
+``--full`` adds the secondary figures.  At W=1 the line then also carries ``w1_rccl_comm``: the same
+step measured a second time with an RCCL communicator initialised and the full W>1 communication path
+running (config 2 of BASELINE.json: "DDP world_size=1 ... RCCL init + HIP kernels"); the headline
+``value`` stays the comm-free step.  ``--comm-figure on`` asks for that figure alone.
+
+``--dump-outputs DIR``: after the timed steps the engine is put back to its seeded start (initial
+parameters, zero optimizer state, first batch) and the timed path runs one more step, the primed
+1-step graph; what that step hands its caller is written as ``DIR/<name>.npy`` (rank 0; float32, the
+float64 / integer meters as float64; at most 64 MB, larger outputs as a fixed seeded sample): the
+updated parameters, the per-row loss and hit flags, and the step's meters.  Model, data and sample
+order depend only on the arguments, so two runs or two builds with the same arguments agree output
+for output up to the step's own rounding (at W=1 the conv1 weight gradients are summed with float
+atomics).  The state after the timed steps themselves is not written: training is chaotic, and the
+few hundred Adam steps of a run amplify that rounding to 1e-4 ... 1e-3 per parameter in the mean.
 """
 from __future__ import annotations
 
@@ -80,7 +92,13 @@ def build_parser():
                     help="graph mode: the first L timed steps replay as 1-step graphs ahead of the multi-step "
                          "graphs, so the GPU starts while the host still submits the long graph (0 = off)")
     ap.add_argument("--comm-figure", choices=["auto", "on", "off"], default="auto",
-                    help="W=1: also time the step with RCCL initialised + the comm path on (auto = on at W=1)")
+                    help="W=1: also time the step with RCCL initialised + the comm path on (auto = with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures (W=1: the w1_rccl_comm figure); a plain run times "
+                         "the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run one step of the timed path from the seeded start state and "
+                         "write what it computed (parameters, per-row loss, meters) as DIR/<name>.npy")
     ap.add_argument("--train-size", type=int, default=60000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--model", choices=["lenet", "gpt2", "resnet18"], default="lenet",
@@ -129,6 +147,45 @@ def _graph_plan(args, S: int) -> str:
     return f"graph replays of {' + '.join(parts)} steps"
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def comm_figure_wanted(args, world: int) -> bool:
+    """The W=1 ``w1_rccl_comm`` figure: asked for by ``--comm-figure on``, or part of ``--full``."""
+    cf = getattr(args, "comm_figure", "auto")
+    if world != 1:
+        return False
+    return cf == "on" or (cf == "auto" and getattr(args, "full", False) and not getattr(args, "force_comm", False))
+
+
+def dump_outputs(directory: str, arrays: dict, cap_bytes: int = DUMP_CAP_BYTES) -> dict:
+    """``--dump-outputs``: write {name: tensor} as ``directory/<name>.npy``.  Floating tensors are
+    written as float32 (float64 stays float64), integer ones as float64.  If everything together
+    would exceed ``cap_bytes``, every array above an equal share of the cap is cut down to a fixed
+    sample of its flattened elements (sorted indices of a seed-0 permutation, the same in every run).
+    Returns {name: elements written}."""
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().to("cpu")
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        host[name] = t.to(torch.float64 if wide else torch.float32).contiguous()
+    written = {}
+    over = sum(t.numel() * t.element_size() for t in host.values()) > cap_bytes
+    share = cap_bytes // max(1, len(host))
+    for name, t in host.items():
+        if over and t.numel() * t.element_size() > share:
+            keep = share // t.element_size()
+            pick = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.reshape(-1)[pick]
+        np.save(os.path.join(directory, name + ".npy"), t.numpy())
+        written[name] = t.numel()
+    return written
+
+
 class _Job:
     """Per-process state shared by the headline run and the W=1 comm figure."""
 
@@ -139,6 +196,7 @@ class _Job:
         self.local_rank = 0 if args.shared_gpu else int(os.environ.get("LOCAL_RANK", "0"))
         self.spin_wait = False
         self.numa = None
+        self.start_state = None
 
 
 def _comm_info(dist, comm, eng):
@@ -309,6 +367,8 @@ def _run_lenet(job: _Job, force_comm: bool, steps: int, warmup: int, comm_world:
     idx = sampler.indices_tensor()
     nfull = idx.numel() // args.batch_size
     eng.set_epoch_indices(idx[: nfull * args.batch_size])   # full batches only: every timed step is B=128
+    if args.dump_outputs:
+        job.start_state = _engine_state(eng)      # the seeded start, for the output step after the window
 
     S = _graph_steps(args)
     Sw = _graph_steps(args, args.warmup) if args.warmup > 0 else 1
@@ -462,6 +522,58 @@ def _w1_anchor(job: _Job):
     return [round(x, 1) for x in v.tolist()]
 
 
+def _engine_state(eng):
+    """The engine's training state (parameters, optimizer moments, step / batch counters, prefetched
+    batches and their parity) as (tensors, copies, parity): what one step reads besides the dataset."""
+    state = [eng.params, eng.m, eng.counters, eng.Xb, eng.Yb, eng.rowsb] + ([eng.v] if eng.v is not eng.m else [])
+    return state, [t.clone() for t in state], eng.q
+
+
+def _step_from_start(job: _Job, eng, comm, start) -> tuple:
+    """``--dump-outputs``: put the engine back to its seeded start (``start``: ``_engine_state`` taken
+    before the first step) and run ONE step through the timed path (the primed 1-step graph, or an
+    eager launch in eager mode; with its collectives at W > 1, so every rank calls this).  Training
+    is chaotic -- the float-atomic conv1 gradient sums differ in rounding from run to run, and a few
+    hundred Adam steps amplify that to 1e-3 per parameter -- so the state after the timed steps is
+    not comparable between runs or builds; one step from the same start is.  Returns that step's
+    (loss_sum, correct)."""
+    import torch
+
+    state, snap, q = start
+    torch.cuda.synchronize()
+    for t, s0 in zip(state, snap):
+        t.copy_(s0)
+    eng.q = q
+    eng.ar_epoch.fill_(-1)              # the optimizer step count repeats: no stale completion word
+    eng.sync_params()
+    eng.reset_meters()
+    if job.args.mode == "graph":
+        eng.replay(steps=1)
+    else:
+        eng.step()
+    torch.cuda.synchronize()
+    if comm is not None:
+        health = comm.health()
+        if health:
+            raise RuntimeError(f"communication failure during the output step: {health}")
+    loss_sum, correct, _ = eng.read_meters()
+    return loss_sum, correct
+
+
+def _lenet_outputs(eng, loss_sum: float, correct: int) -> dict:
+    """What the training step hands its caller: the parameters it updated (the model's own tensors),
+    the step's per-row loss / hit flags, and the meters."""
+    import torch
+
+    out = {"loss_sum": torch.tensor([loss_sum], dtype=torch.float64),
+           "correct": torch.tensor([correct], dtype=torch.int64)}
+    net = getattr(eng, "net", None)
+    if net is not None:
+        out.update({"param." + n: p for n, p in net.named_parameters()})
+        out.update(row_loss=eng.row_loss, row_hit=eng.row_hit)
+    return out
+
+
 def lenet_main(job: _Job):
     import torch
 
@@ -486,6 +598,10 @@ def lenet_main(job: _Job):
     if bad:
         raise RuntimeError(f"rank placement check failed: {bad}")
     loss_sum, correct, _ = eng.read_meters()
+    if args.dump_outputs:
+        o_loss, o_correct = (loss_sum, correct) if stub else _step_from_start(job, eng, comm, job.start_state)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, _lenet_outputs(eng, o_loss, o_correct))
     n_img = args.steps * args.batch_size * world
     ips = n_img / elapsed
     S = _graph_steps(args)
@@ -529,8 +645,7 @@ def lenet_main(job: _Job):
         out["scaling_eff_same_job"] = round(ips / world / a1, 4)
     if stub:
         out["data"] = "STUB (PDE_BENCH_STUB=1: CPU control-flow test, sleep per step, not a measurement)"
-    want_fig = args.comm_figure == "on" or (args.comm_figure == "auto" and world == 1 and not args.force_comm)
-    if want_fig and world == 1:
+    if comm_figure_wanted(args, world):
         # config 2 (BASELINE.json): the same step with RCCL initialised and the comm path running
         try:
             e2, eng2, comm2, extra2 = _run_lenet(job, True, args.steps, args.warmup, True)

@@ -56,8 +56,22 @@ def _w1_comm_group(dist):
 
 
 def _comm_figure_wanted(args, world) -> bool:
+    """The W = 1 ``w1_rccl_comm`` figure: ``--comm-figure on``, or ``--full`` with ``--comm-figure auto``."""
     cf = getattr(args, "comm_figure", "auto")
-    return world == 1 and not getattr(args, "force_comm", False) and cf in ("auto", "on")
+    asked = cf == "on" or (cf == "auto" and getattr(args, "full", False))
+    return world == 1 and not getattr(args, "force_comm", False) and asked
+
+
+def _dump(args, rank, model, last_loss):
+    """``--dump-outputs``: the parameters the timed steps trained (one flat vector in registration
+    order, a fixed seeded sample when above the size cap) and the last timed step's loss."""
+    if not getattr(args, "dump_outputs", None) or rank != 0:
+        return
+    import torch
+
+    from bench import dump_outputs
+    flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    dump_outputs(args.dump_outputs, {"params": flat, "last_loss": torch.tensor([last_loss], dtype=torch.float64)})
 
 
 def _graph_wanted(args) -> bool:
@@ -217,13 +231,14 @@ def _gpt2_run(args, torch, dist, rank, world, dev, comm):
     if comm:
         ddp.check_health()
     return {"elapsed": elapsed, "extra": extra, "B": B, "T": T, "flops_per_token": model.flops_per_token(),
-            "last_loss": float(losses[-1])}
+            "last_loss": float(losses[-1]), "model": model}
 
 
 def bench_gpt2(args):
     torch, dist, rank, world, dev = _setup(getattr(args, "shared_gpu", False), getattr(args, "numa_bdf", None))
     r = _gpt2_run(args, torch, dist, rank, world, dev, comm=world > 1 or getattr(args, "force_comm", False))
     B, T = r["B"], r["T"]
+    _dump(args, rank, r.pop("model"), r["last_loss"])
     tps = args.steps * B * T * world / r["elapsed"]
     out = {
         "metric": "tokens/sec (whole node), GPT-2-small DDP",

@@ -6,7 +6,7 @@ from __future__ import annotations
 import json
 
 import bench_models
-from bench_models import (_cap, _capture_step, _comm_figure_wanted, _graph_wanted, _setup, _timed, _tune,
+from bench_models import (_cap, _capture_step, _comm_figure_wanted, _dump, _graph_wanted, _setup, _timed, _tune,
                           _w1_comm_group)
 
 
@@ -69,13 +69,14 @@ def _resnet_run(args, torch, dist, rank, world, dev, comm):
     elapsed = _timed(torch, dist, world, step, args.warmup, args.steps)
     if comm:
         ddp.check_health()
-    return {"elapsed": elapsed, "extra": extra, "B": B, "last_loss": float(losses[-1])}
+    return {"elapsed": elapsed, "extra": extra, "B": B, "last_loss": float(losses[-1]), "model": model}
 
 
 def bench_resnet18(args):
     torch, dist, rank, world, dev = _setup(getattr(args, "shared_gpu", False), getattr(args, "numa_bdf", None))
     r = _resnet_run(args, torch, dist, rank, world, dev, comm=world > 1 or getattr(args, "force_comm", False))
     B = r["B"]
+    _dump(args, rank, r.pop("model"), r["last_loss"])
     ips = args.steps * B * world / r["elapsed"]
     out = {
         "metric": "images/sec (whole node), ResNet-18 bf16 DDP",

@@ -275,3 +275,72 @@ def test_bench_replay_plan():
             plan = bench._replay_plan(n, S, L)
             assert sum(plan) == n and plan[:L] == [1] * L
             assert set(plan) <= {S, (n - L) % S or 1, 1}
+
+
+def test_bench_secondary_figure_only_with_full():
+    """A plain run measures the headline alone: the W=1 comm figure belongs to ``--full`` (or to an
+    explicit ``--comm-figure on``), never to W > 1 and never to an automatic ``--force-comm`` run."""
+    import bench
+    parse = lambda *a: bench.build_parser().parse_args(list(a))
+    assert not bench.comm_figure_wanted(parse("--gpus", "1", "--steps", "20", "--warmup", "5"), 1)
+    assert bench.comm_figure_wanted(parse("--full"), 1)
+    assert bench.comm_figure_wanted(parse("--comm-figure", "on"), 1)
+    assert not bench.comm_figure_wanted(parse("--full", "--comm-figure", "off"), 1)
+    assert not bench.comm_figure_wanted(parse("--full", "--force-comm"), 1)
+    assert not bench.comm_figure_wanted(parse("--full", "--gpus", "2"), 2)
+    import bench_models
+    assert not bench_models._comm_figure_wanted(parse("--model", "gpt2"), 1)
+    assert bench_models._comm_figure_wanted(parse("--model", "gpt2", "--full"), 1)
+    assert bench_models._comm_figure_wanted(parse("--model", "gpt2", "--comm-figure", "on"), 1)
+    assert not bench_models._comm_figure_wanted(parse("--model", "gpt2", "--full", "--comm-figure", "off"), 1)
+
+
+def test_bench_dump_outputs_dtypes_cap_and_fixed_sample(tmp_path):
+    """``--dump-outputs``: one .npy per name, float32 (float64 / integers as float64), everything
+    within the byte cap, and an array above its share cut to the same seeded sample on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+    big = torch.arange(1000, dtype=torch.float32) * 0.5
+    arrays = {"w": big, "half": torch.ones(3, dtype=torch.bfloat16), "count": torch.tensor([7], dtype=torch.int64),
+              "meter": torch.tensor([1.25], dtype=torch.float64)}
+    n = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert n == {"w": 1000, "half": 3, "count": 1, "meter": 1}
+    assert got["w"].dtype == np.float32 and got["half"].dtype == np.float32
+    assert got["count"].dtype == np.float64 and got["meter"].dtype == np.float64
+    assert np.array_equal(got["w"], big.numpy()) and got["count"][0] == 7.0 and got["meter"][0] == 1.25
+    # capped at 1600 bytes: 400 per array, so w keeps 100 of its 1000 elements, the small ones stay whole
+    n = bench.dump_outputs(str(tmp_path / "b"), arrays, cap_bytes=1600)
+    assert n == {"w": 100, "half": 3, "count": 1, "meter": 1}
+    bench.dump_outputs(str(tmp_path / "c"), arrays, cap_bytes=1600)
+    wb, wc = np.load(tmp_path / "b" / "w.npy"), np.load(tmp_path / "c" / "w.npy")
+    assert wb.shape == (100,) and np.array_equal(wb, wc)
+    assert np.all(np.diff(wb) > 0) and np.isin(wb, big.numpy()).all()      # distinct elements, in order
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "b").iterdir()) <= 1600
+
+
+def test_bench_stub_plain_run_dumps_and_reports_ms_per_step(tmp_path):
+    """``bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`` (CPU stub engine): one result line
+    with ``ms_per_step`` for the K timed steps, no secondary figure, and the meters written."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PDE_BENCH_STUB="1", PDE_BENCH_NUMA="0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup",
+                        "5", "--no-spin-wait", "--dump-outputs", str(tmp_path / "out")], capture_output=True,
+                       text=True, env=env, timeout=180)
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert p.returncode == 0 and len(lines) == 1, (p.stdout, p.stderr[-2000:])
+    d = json.loads(lines[0])
+    assert d["steps"] == 20 and d["ms_per_step"] > 0 and "w1_rccl_comm" not in d
+    assert abs(d["value"] - 128 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    assert sorted(os.listdir(tmp_path / "out")) == ["correct.npy", "loss_sum.npy"]
+    assert np.load(tmp_path / "out" / "loss_sum.npy").dtype == np.float64

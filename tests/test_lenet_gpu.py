@@ -349,3 +349,68 @@ def test_engine_rejects_unknown_bwd_mode(monkeypatch):
     with pytest.raises(ValueError):
         LeNetTrainStep(build_net(seed=1, device=DEV), batch_size=128)
 
+
+
+def test_bench_plain_run_dumps_reproducible_step_outputs(tmp_path, capsys, monkeypatch):
+    """``bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR``: a plain run prints one result line
+    for the K timed steps without the ``--full`` figures, then writes what one step of the timed path
+    computes from the seeded start state (updated parameters, per-row loss / hit flags, meters) as
+    float32 / float64 .npy files -- the same from run to run, whatever K and W were.
+    (``bench.main`` in this process: no second interpreter start; the host-thread pinning and wait
+    policy it would set for a process of its own stay off.)
+
+    Bound between two runs: everything but the conv1 gradient sums (float atomics) is computed in a
+    fixed order, and Adam's first update lr * g / (|g| + eps) moves with a rounding difference d in g
+    by lr * eps * d / (|g| + eps)^2 -- below 1e-9 unless |g| is itself within rounding of zero, where
+    it can reach the whole step.  So at least 99 % of every array agree within 1e-6 (float32
+    resolution of parameters below 1) and no element differs by more than 2 * lr; the losses come
+    from the forward pass of the identical start state and agree to float32 rounding."""
+    import json
+    import os
+
+    import numpy as np
+
+    import bench
+    monkeypatch.setenv("PDE_BENCH_NUMA", "0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "PDE_BENCH_STUB", "PDE_BENCH_RESULT"):
+        monkeypatch.delenv(k, raising=False)
+    shapes = {"param." + n: tuple(q.shape) for n, q in build_net(seed=0, device="cpu").named_parameters()}
+    shapes.update(row_loss=(128,), row_hit=(128,), loss_sum=(1,), correct=(1,))
+    runs = []
+    for name, steps, warmup in (("a", "4", "2"), ("b", "7", "3")):
+        out = tmp_path / name
+        capsys.readouterr()
+        bench.main(["--gpus", "1", "--steps", steps, "--warmup", warmup, "--train-size", "2048", "--no-spin-wait",
+                    "--dump-outputs", str(out)])
+        lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["steps"] == int(steps) and d["ms_per_step"] > 0 and d["dtype"] == "fp32" and "w1_rccl_comm" not in d
+        assert abs(d["value"] - 128 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+        assert 0 < d["train_loss_mean_timed_rank0"] < 10           # the line's meters are the timed steps'
+        assert sorted(os.listdir(out)) == sorted(k + ".npy" for k in shapes)
+        got = {k: np.load(out / (k + ".npy")) for k in shapes}
+        for k, a in got.items():
+            assert a.shape == shapes[k] and np.isfinite(a).all(), k
+            assert a.dtype == (np.float64 if k in ("loss_sum", "correct", "row_hit") else np.float32), k
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        assert set(np.unique(got["row_hit"])) <= {0.0, 1.0} and (got["row_loss"] >= 0).all()
+        # the dumped meters are those of the one output step of 128 rows
+        assert abs(got["loss_sum"][0] - got["row_loss"].astype(np.float64).sum()) <= 1e-3
+        assert got["correct"][0] == got["row_hit"].sum()
+        runs.append(got)
+    # the step really trained: the parameters left the seeded initial values by about lr
+    init = dict(build_net(seed=0, device="cpu").named_parameters())
+    moved = np.abs(runs[0]["param.fc1.weight"] - init["fc1.weight"].detach().numpy())
+    assert 1e-4 < moved.mean() <= 1.01e-3
+    for k in shapes:
+        diff = np.abs(runs[0][k].astype(np.float64) - runs[1][k].astype(np.float64)).reshape(-1)
+        print(f"{k}: max diff {diff.max():.3e}, above 1e-6: {(diff > 1e-6).sum()} of {diff.size}")
+        if k.startswith("param."):
+            assert (diff <= 1e-6).mean() >= 0.99 and diff.max() <= 2e-3, k
+        elif k == "loss_sum":
+            assert diff.max() <= 1e-3, k             # 128 float32 losses of order 1, summed in float64
+        elif k == "row_loss":
+            assert diff.max() <= 1e-5, k
+        else:
+            assert diff.max() == 0, k

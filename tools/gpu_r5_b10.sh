@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest -x -q --timeout 240 --timeout-method threa
   > $O/pytest_peer.txt 2>&1 || { tail -30 $O/pytest_peer.txt; exit 1; }
 tail -2 $O/pytest_peer.txt
 for m in graph eager graph; do
-  PDE_ROUTE_TIMING=$m timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/lenet_$m.json 2> $O/lenet_$m.err || exit 1
+  PDE_ROUTE_TIMING=$m timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > $O/lenet_$m.json 2> $O/lenet_$m.err || exit 1
   python - $O/lenet_$m.json $m <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); w = d.get("w1_rccl_comm", {})

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 timeout -k 10 900 python -u -m pytest -x -v --timeout 170 --timeout-method thread tests/test_peer_gpu.py \
   > $O/pytest_peer.txt 2>&1 || { tail -40 $O/pytest_peer.txt; exit 1; }
 tail -2 $O/pytest_peer.txt
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/lenet.json 2> $O/lenet.err || exit 1
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > $O/lenet.json 2> $O/lenet.err || exit 1
 python - $O/lenet.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); w = d.get("w1_rccl_comm", {})
@@ -17,7 +17,7 @@ print("lenet headline", d["ms_per_step"], "| comm", w.get("ms_per_step"), w.get(
       "compute", w.get("compute_only_us_per_step"), "routes", json.dumps(w.get("route_us_per_call")))
 PY
 for m in gpt2 resnet18; do
-  timeout -k 10 400 python bench.py --model $m --steps 20 --warmup 5 > $O/$m.json 2> $O/$m.err || exit 1
+  timeout -k 10 400 python bench.py --model $m --steps 20 --warmup 5 --full > $O/$m.json 2> $O/$m.err || exit 1
   python - $O/$m.json $m <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); w = d.get("w1_rccl_comm", {})

@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 240 --timeout-method threa
   > $O/pytest_peer.txt 2>&1 || { tail -30 $O/pytest_peer.txt; exit 1; }
 tail -3 $O/pytest_peer.txt
 for v in 1 2 4; do
-  PDE_PEER_IP_VPT=$v timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/lenet_vpt$v.json 2> $O/lenet_vpt$v.err || exit 1
+  PDE_PEER_IP_VPT=$v timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > $O/lenet_vpt$v.json 2> $O/lenet_vpt$v.err || exit 1
   python - $O/lenet_vpt$v.json $v <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); w = d.get("w1_rccl_comm", {})

@@ -12,7 +12,7 @@ f=$(find $O/tr_pfold -name "*kernel_trace.csv" | head -1)
 python3 tools/trace_summary.py "$f" k_conv_fwd2 10 > $O/timeline_pfold.txt || exit 1
 rm -f "$f"
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_$i.json 2> $O/bench_$i.err || exit 1
+  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > $O/bench_$i.json 2> $O/bench_$i.err || exit 1
 done
 timeout -k 10 300 python bench.py --model gpt2 --steps 20 --warmup 5 > $O/gpt2_A.json 2> $O/gpt2_A.err || exit 1
 PDE_GEMM_CFG="fprop:2304:768=22,dgrad:768:2304=19" timeout -k 10 300 python bench.py --model gpt2 --steps 20 --warmup 5 > $O/gpt2_B.json 2> $O/gpt2_B.err || exit 1
