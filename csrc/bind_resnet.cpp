@@ -216,7 +216,8 @@ void bnpool_bwd(const at::Tensor& dp, const at::Tensor& arg, const at::Tensor& y
 }
 
 void sgd_master(const at::Tensor& master, const at::Tensor& p16, const at::Tensor& g16, const at::Tensor& buf,
-                double lr, double momentum, double wd, bool nesterov, double grad_scale, const OptT& decay_blk) {
+                double lr, double momentum, double wd, bool nesterov, double grad_scale, const OptT& decay_blk,
+                int64_t step, const OptT& step_dev, const OptT& arrive, const OptT& lr_tab) {
   const int64_t n = master.numel();
   TORCH_CHECK(n % 64 == 0, "sgd_master: flat buffers are padded to 64 elements");
   check_cuda(master, "master", F32);
@@ -224,8 +225,16 @@ void sgd_master(const at::Tensor& master, const at::Tensor& p16, const at::Tenso
   check_cuda(g16, "grad_bf16", BF16, n);
   check_cuda(buf, "momentum_buffer", F32, n);
   const uint8_t* db = optr<uint8_t>(decay_blk, "decay_blk", U8, n / 64);
+  // step_dev (the capturable device step count) is advanced by the kernel; arrive is its fan-in counter
+  float* sd = optr<float>(step_dev, "step_dev", F32, 1);
+  unsigned* arr = optr<unsigned>(arrive, "arrive", I32, 1);
+  TORCH_CHECK((sd == nullptr) == (arr == nullptr), "sgd_master: step_dev and arrive go together");
+  int lr_len = 0;
+  const float* lrt = lr_table(lr_tab, master, &lr_len);
   hip_check(pde_sgd_master(ptr<float>(master), p16.data_ptr(), g16.data_ptr(), ptr<float>(buf), n, (float)lr,
-                           (float)momentum, (float)wd, nesterov, (float)grad_scale, db, cur_stream()),
+                           (float)momentum, (float)wd, nesterov, (float)grad_scale, db, (int)step, sd, arr, lrt,
+                           lr_len,
+                           cur_stream()),
             "sgd_master");
 }
 
@@ -454,7 +463,10 @@ void register_resnet(pybind11::module& m) {
         py::arg("rstd"), py::arg("part"), py::arg("coef"), py::arg("dgamma"), py::arg("dbeta"), py::arg("dx"),
         py::arg("dres"), py::arg("relu"), py::arg("scale") = py::none(), py::arg("shift") = py::none(),
         py::arg("pre_nblk") = 0);
-  m.def("sgd_master", &sgd_master);
+  m.def("sgd_master", &sgd_master, py::arg("master"), py::arg("p16"), py::arg("g16"), py::arg("buf"), py::arg("lr"),
+        py::arg("momentum"), py::arg("wd"), py::arg("nesterov"), py::arg("grad_scale"), py::arg("decay_blk"),
+        py::arg("step") = 0, py::arg("step_dev") = py::none(), py::arg("arrive") = py::none(),
+        py::arg("lr_table") = py::none());
   m.def("maxpool3s2_fwd", &maxpool3s2_fwd);
   m.def("avgpool_fwd", &avgpool_fwd);
   m.def("avgpool_bwd", &avgpool_bwd);

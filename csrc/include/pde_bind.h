@@ -28,6 +28,21 @@ inline T* optr(const OptT& t, const char* name, at::ScalarType dt, int64_t min_n
   return ptr<T>(*t);
 }
 
+// Optional learning-rate table of the optimizer kernels (pde_lr.h): fp32, at least one entry, on the
+// parameters' device.  Returns null (and *len = 0) when no table is given.
+inline const float* lr_table(const OptT& t, const at::Tensor& params, int* len) {
+  *len = 0;
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->scalar_type() == at::kFloat, "lr_table has dtype ", t->scalar_type(), ", expected float32");
+  TORCH_CHECK(t->device() == params.device(), "lr_table is on ", t->device(), ", the parameters are on ",
+              params.device());
+  TORCH_CHECK(t->dim() == 1 && t->is_contiguous(), "lr_table must be a contiguous 1-D tensor");
+  TORCH_CHECK(t->numel() >= 1, "lr_table is empty: it needs at least one learning rate");
+  TORCH_CHECK(t->numel() <= INT32_MAX, "lr_table has too many entries");
+  *len = (int)t->numel();
+  return ptr<float>(*t);
+}
+
 inline void hip_check(hipError_t e, const char* what) {
   TORCH_CHECK(e == hipSuccess, what, " failed: ", hipGetErrorString(e));
 }

@@ -40,17 +40,19 @@ unsigned long long* pde_lenet_prof_slot(int kid);
 // ---- optimizers: csrc/kernels/optim.hip ----
 // fold_*: gradient replicas folded before the update: for e in [fold_off, fold_off + fold_len),
 // g[e] = sum_{r < fold_nrep} g[e + r * fold_stride] (written back); replica storage r >= 1 is skipped.
+// lr_tab / lr_len (all four optimizers; nullable): device table of per-step learning rates, optimizer step t
+// (1-based) uses lr_tab[min(t-1, lr_len-1)] in place of the by-value lr (pde_lr.h).
 hipError_t pde_adam_flat(float* p, float* g, float* m, float* v, long long n, float lr, float b1, float b2,
                          float eps, float wd, int decoupled, float grad_scale, long long* step, unsigned* arrive,
                          int bump, long long pack_off, float* pack_dst, long long fold_off, int fold_len,
                          int fold_nrep, int fold_stride, const void* peer_dev, long long ar_off,
                          long long* ar_epoch, int ar_two, int pack_mode, long long fold2_off, int fold2_len,
-                         int fold2_nrep, int fold2_stride, hipStream_t st);
+                         int fold2_nrep, int fold2_stride, const float* lr_tab, int lr_len, hipStream_t st);
 hipError_t pde_sgd_flat(float* p, float* g, float* buf, long long n, float lr, float momentum, float dampening,
                         float wd, int nesterov, float grad_scale, long long* step, unsigned* arrive, int bump,
                         long long pack_off, float* pack_dst, long long fold_off, int fold_len, int fold_nrep,
                         int fold_stride, int pack_mode, long long fold2_off, int fold2_len, int fold2_nrep,
-                        int fold2_stride, hipStream_t st);
+                        int fold2_stride, const float* lr_tab, int lr_len, hipStream_t st);
 hipError_t pde_lenet_pack_w2(const float* w2, float* dst, hipStream_t st);
 
 // ---- LeNet step v2: csrc/kernels/lenet_v2.hip ----
@@ -139,7 +141,7 @@ hipError_t pde_sumsq_bf16(const void* g, int64_t n, float scale, float* out, flo
 hipError_t pde_adamw_master(float* master, void* p16, const void* g16, float* m, float* v, int64_t n, float lr,
                             float b1, float b2, float eps, float wd, float grad_scale, int step,
                             const uint8_t* decay_blk, const float* clip_sumsq, float max_norm, const float* step_dev,
-                            hipStream_t st);
+                            const float* lr_tab, int lr_len, hipStream_t st);
 hipError_t pde_f32_to_bf16(const float* x, void* y, int64_t n, hipStream_t st);
 hipError_t pde_scale_bf16(void* x, const float* s, int64_t n, hipStream_t st);   // x *= s[0], n % 8 == 0
 hipError_t pde_sum_f32(const float* x, int n, float* out, float scale, hipStream_t st);
@@ -220,7 +222,8 @@ hipError_t pde_maxpool3s2_bwd(const void* dy, const void* arg, void* dx, int N, 
 hipError_t pde_avgpool_fwd(const void* x, void* out, int N, int HW, int C, hipStream_t st);
 hipError_t pde_avgpool_bwd(const void* dout, void* dx, int N, int HW, int C, hipStream_t st);
 hipError_t pde_sgd_master(float* master, void* p16, const void* g16, float* buf, int64_t n, float lr, float momentum,
-                          float wd, int nesterov, float grad_scale, const uint8_t* decay_blk, hipStream_t st);
+                          float wd, int nesterov, float grad_scale, const uint8_t* decay_blk, int step,
+                          float* step_dev, unsigned* arrive, const float* lr_tab, int lr_len, hipStream_t st);
 
 #ifdef __cplusplus
 }

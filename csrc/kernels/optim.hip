@@ -8,6 +8,8 @@
 // step is capturable in a hipGraph and replayable without host involvement.  `bump` = number of
 // consecutive int64 counters advanced by the last block (0: none; [0] is the optimizer step);
 // bump < 0: the caller's earlier kernel already advanced the counter, t = *step, no fan-in at all.
+// lr_tab (nullable): a device table of per-step learning rates, step t uses lr_tab[min(t-1, lr_len-1)]
+// (pde_lr.h), so a captured launch follows a schedule; null = the by-value lr.
 // grad_scale folds the DDP 1/world_size average (or any loss scale) into the update.
 // Optional fused all-reduce (Adam only, the W > 1 "fused" LeNet schedule): the first ar_nvb blocks
 // all-reduce the flat range [ar_lo4, n4) (the conv-gradient bucket) across ranks with the xGMI peer
@@ -21,6 +23,7 @@
 #include "pde_lenet.h"
 #include "pde_peer_dev.h"
 #include "pde_adam.h"
+#include "pde_lr.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -184,11 +187,13 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, float* __re
                                               float lr, float b1, float b2, float eps, float wd, int decoupled,
                                               float grad_scale, long long* __restrict__ step,
                                               unsigned* __restrict__ arrive, int bump, Pack pk, Fold fd, FusedAR ar,
-                                              unsigned long long* __restrict__ prof) {
+                                              unsigned long long* __restrict__ prof,
+                                              const float* __restrict__ lr_tab, int lr_len) {
   if constexpr (PROF) {
     if (threadIdx.x == 0) prof[(size_t)blockIdx.x * 8] = __builtin_amdgcn_s_memrealtime();
   }
   const long long t = bump < 0 ? *step : *step + 1;   // bump < 0: counter pre-advanced by an earlier kernel
+  lr = sched_lr(lr, lr_tab, lr_len, t);
   __shared__ uint32_t lds2[2];
   const Holes holes = make_holes(fd);
   const long long n4c = n4 - holes.len[0] - holes.len[1];   // compressed index space (replicas skipped)
@@ -296,8 +301,10 @@ __device__ __forceinline__ void sgd_elem(float& p, float& b, float d, float lr, 
 __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
                                              long long n4, float lr, float momentum, float dampening, float wd,
                                              int nesterov, float grad_scale, long long* __restrict__ step,
-                                             unsigned* __restrict__ arrive, int bump, Pack pk, Fold fd) {
+                                             unsigned* __restrict__ arrive, int bump, Pack pk, Fold fd,
+                                             const float* __restrict__ lr_tab, int lr_len) {
   const long long t = bump < 0 ? *step : *step + 1;
+  lr = sched_lr(lr, lr_tab, lr_len, t);
   float4* p4 = reinterpret_cast<float4*>(p);
   float4* g4 = reinterpret_cast<float4*>(g);
   float4* b4 = reinterpret_cast<float4*>(buf);
@@ -367,8 +374,9 @@ hipError_t pde_adam_flat(float* p, float* g, float* m, float* v, long long n, fl
                          int bump, long long pack_off, float* pack_dst, long long fold_off, int fold_len,
                          int fold_nrep, int fold_stride, const void* peer_dev, long long ar_off, long long* ar_epoch,
                          int ar_two, int pack_mode, long long fold2_off, int fold2_len, int fold2_nrep,
-                         int fold2_stride, hipStream_t st) {
+                         int fold2_stride, const float* lr_tab, int lr_len, hipStream_t st) {
   if (n % 4) return hipErrorInvalidValue;
+  if (lr_tab != nullptr && lr_len < 1) return hipErrorInvalidValue;
   const long long n4 = n / 4;
   FusedAR ar{};
   if (peer_dev != nullptr && ar_epoch != nullptr) {
@@ -399,7 +407,7 @@ hipError_t pde_adam_flat(float* p, float* g, float* m, float* v, long long n, fl
                      b2, eps, wd, decoupled, grad_scale, step, arrive, bump, Pack{pack_off, pack_dst, pack_mode},    \
                      Fold{{Fold1{fold_off, fold_len, fold_nrep, fold_stride},                                      \
                            Fold1{fold2_off, fold2_len, fold2_nrep, fold2_stride}}},                                \
-                     ar, P ? prof : nullptr)
+                     ar, P ? prof : nullptr, lr_tab, lr_len)
   if (prof) {
     if (ntp) PDE_ADAM_LAUNCH(true, true); else PDE_ADAM_LAUNCH(true, false);
   } else {
@@ -413,8 +421,9 @@ hipError_t pde_sgd_flat(float* p, float* g, float* buf, long long n, float lr, f
                         float wd, int nesterov, float grad_scale, long long* step, unsigned* arrive, int bump,
                         long long pack_off, float* pack_dst, long long fold_off, int fold_len, int fold_nrep,
                         int fold_stride, int pack_mode, long long fold2_off, int fold2_len, int fold2_nrep,
-                        int fold2_stride, hipStream_t st) {
+                        int fold2_stride, const float* lr_tab, int lr_len, hipStream_t st) {
   if (n % 4) return hipErrorInvalidValue;
+  if (lr_tab != nullptr && lr_len < 1) return hipErrorInvalidValue;
   const long long n4 = n / 4;
   const Fold fdh{{Fold1{fold_off, fold_len, fold_nrep, fold_stride}, Fold1{fold2_off, fold2_len, fold2_nrep, fold2_stride}}};
   const Holes hh = make_holes(fdh);
@@ -425,7 +434,8 @@ hipError_t pde_sgd_flat(float* p, float* g, float* buf, long long n, float lr, f
   const int nfb = fold_blocks(fdh.f[0]) + fold_blocks(fdh.f[1]);
   hipLaunchKernelGGL(k_sgd, dim3(grid_for(n4 - hh.len[0] - hh.len[1]) + nfb), dim3(256), 0, st, p, g, buf, n4, lr, momentum, dampening, wd,
                      nesterov, grad_scale, step, arrive, bump, Pack{pack_off, pack_dst, pack_mode},
-                     Fold{{Fold1{fold_off, fold_len, fold_nrep, fold_stride}, Fold1{fold2_off, fold2_len, fold2_nrep, fold2_stride}}});
+                     Fold{{Fold1{fold_off, fold_len, fold_nrep, fold_stride}, Fold1{fold2_off, fold2_len, fold2_nrep, fold2_stride}}},
+                     lr_tab, lr_len);
   return hipGetLastError();
 }
 

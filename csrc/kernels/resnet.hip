@@ -10,6 +10,7 @@
 #include "pde_hip.h"
 #include "pde_bf16.h"
 #include "pde_kernels.h"
+#include "pde_lr.h"
 
 namespace {
 
@@ -695,7 +696,15 @@ __global__ __launch_bounds__(256, 3) void k_bnpool_bwd(const uint4* __restrict__
 __global__ __launch_bounds__(256) void k_sgd_master(float* __restrict__ master, uint2* __restrict__ p16,
                                                     const uint2* __restrict__ g16, float4* __restrict__ buf, int64_t n4,
                                                     float lr, float momentum, float wd, int nesterov, float grad_scale,
-                                                    const uint8_t* __restrict__ decay_blk) {
+                                                    const uint8_t* __restrict__ decay_blk, int step,
+                                                    float* __restrict__ step_dev, unsigned* __restrict__ arrive,
+                                                    const float* __restrict__ lr_tab, int lr_len) {
+  // the update needs no step count: step / step_dev (nullable, the capturable device count) only select
+  // the entry of the nullable learning-rate table (pde_lr.h).  The device count is advanced here, as
+  // k_adam does (optim.hip): every block reads t = *step_dev + 1 and the last block to arrive publishes
+  // it and resets the arrival counter, so a captured step counts on every replay with no extra launch.
+  if (step_dev) step = (int)*step_dev + 1;
+  lr = sched_lr(lr, lr_tab, lr_len, step);
   float4* mp = reinterpret_cast<float4*>(master);
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     float4 p = mp[i], b = buf[i];
@@ -713,6 +722,21 @@ __global__ __launch_bounds__(256) void k_sgd_master(float* __restrict__ master, 
     mp[i] = p;
     buf[i] = b;
     p16[i] = pack4(pp);
+  }
+  if (step_dev) {                                  // block-uniform (kernel argument)
+    __shared__ int is_last;
+    __syncthreads();                               // every wave of the block has read the count
+    if (threadIdx.x == 0) {
+      // the arrival add depends on the step value this block read, so it cannot be issued before that
+      // read returned: no block can observe the advanced count
+      const unsigned prev = atomicAdd(arrive, step > 0 ? 1u : 2u);
+      is_last = (prev == gridDim.x - 1);
+    }
+    __syncthreads();
+    if (is_last && threadIdx.x == 0) {
+      *step_dev = (float)step;
+      *arrive = 0u;
+    }
   }
 }
 
@@ -946,10 +970,14 @@ hipError_t pde_maxpool3s2_bwd(const void* dy, const void* arg, void* dx, int N, 
 }
 
 hipError_t pde_sgd_master(float* master, void* p16, const void* g16, float* buf, int64_t n, float lr, float momentum,
-                          float wd, int nesterov, float grad_scale, const uint8_t* decay_blk, hipStream_t st) {
+                          float wd, int nesterov, float grad_scale, const uint8_t* decay_blk, int step,
+                          float* step_dev, unsigned* arrive, const float* lr_tab, int lr_len, hipStream_t st) {
+  if (lr_tab != nullptr && lr_len < 1) return hipErrorInvalidValue;
+  if ((step_dev == nullptr) != (arrive == nullptr)) return hipErrorInvalidValue;
   const int64_t n4 = n / 4;
   hipLaunchKernelGGL(k_sgd_master, dim3(grid_cap(n4, 2048)), dim3(256), 0, st, master, (uint2*)p16,
-                     (const uint2*)g16, (float4*)buf, n4, lr, momentum, wd, nesterov, grad_scale, decay_blk);
+                     (const uint2*)g16, (float4*)buf, n4, lr, momentum, wd, nesterov, grad_scale, decay_blk, step,
+                     step_dev, arrive, lr_tab, lr_len);
   return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include "pde_act.h"
 #include "pde_bf16.h"
 #include "pde_kernels.h"
+#include "pde_lr.h"
 
 namespace {
 
@@ -668,9 +669,11 @@ __global__ __launch_bounds__(256) void k_adamw_master(float* __restrict__ master
                                                       float b2, float eps, float wd, float grad_scale, int step,
                                                       const uint8_t* __restrict__ decay_blk,
                                                       const float* __restrict__ clip_sumsq, float max_norm,
-                                                      const float* __restrict__ step_dev) {
+                                                      const float* __restrict__ step_dev,
+                                                      const float* __restrict__ lr_tab, int lr_len) {
   float gs = grad_scale;
   if (step_dev) step = (int)*step_dev;               // capturable mode: the step count lives on the device
+  lr = sched_lr(lr, lr_tab, lr_len, step);           // nullable per-step learning-rate table (pde_lr.h)
   if (clip_sumsq) {
     const float norm = sqrtf(*clip_sumsq);
     gs *= fminf(1.f, max_norm / (norm + 1e-6f));
@@ -960,11 +963,12 @@ hipError_t pde_sumsq_bf16(const void* g, int64_t n, float scale, float* out, flo
 hipError_t pde_adamw_master(float* master, void* p16, const void* g16, float* m, float* v, int64_t n, float lr,
                             float b1, float b2, float eps, float wd, float grad_scale, int step,
                             const uint8_t* decay_blk, const float* clip_sumsq, float max_norm, const float* step_dev,
-                            hipStream_t st) {
+                            const float* lr_tab, int lr_len, hipStream_t st) {
+  if (lr_tab != nullptr && lr_len < 1) return hipErrorInvalidValue;
   const int64_t n4 = n / 4;
   hipLaunchKernelGGL(k_adamw_master, dim3(grid_for(n4, 256, 2048)), dim3(256), 0, st, master, (uint2*)p16,
                      (const uint2*)g16, (float4*)m, (float4*)v, n4, lr, b1, b2, eps, wd, grad_scale, step, decay_blk,
-                     clip_sumsq, max_norm, step_dev);
+                     clip_sumsq, max_norm, step_dev, lr_tab, lr_len);
   return hipGetLastError();
 }
 

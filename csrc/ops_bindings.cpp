@@ -204,7 +204,7 @@ void adam_flat(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, co
                const at::Tensor& arrive, int64_t bump, int64_t pack_off, const OptT& pack_dst, int64_t fold_off,
                int64_t fold_len, int64_t fold_nrep, int64_t fold_stride, const OptT& peer_dev, int64_t ar_off,
                const OptT& ar_epoch, int64_t ar_two, int64_t pack_mode, int64_t fold2_off, int64_t fold2_len,
-               int64_t fold2_nrep, int64_t fold2_stride) {
+               int64_t fold2_nrep, int64_t fold2_stride, const OptT& lr_tab) {
   const int64_t n = p.numel();
   // fused all-reduce of [ar_off, n) by side blocks (peer_dev = CPU bytes of PeerAllReduce.device_args())
   const void* pdev = nullptr;
@@ -223,6 +223,8 @@ void adam_flat(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, co
     ep = ptr<long long>(*ar_epoch);
   }
   check_cuda(p, "params", F32);
+  int lr_len = 0;
+  const float* lrt = pde::lr_table(lr_tab, p, &lr_len);
   check_cuda(g, "grads", F32, n);
   check_cuda(m, "exp_avg", F32, n);
   if (fold_off >= 0 && fold_nrep > 1)
@@ -245,7 +247,7 @@ void adam_flat(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, co
                           (float)b2, (float)eps, (float)wd, decoupled ? 1 : 0, (float)grad_scale, ptr<long long>(step),
                           ptr<unsigned>(arrive), (int)bump, pd ? pack_off : -1, pd, fold_off, (int)fold_len,
                           (int)fold_nrep, (int)fold_stride, pdev, ar_off, ep, (int)ar_two, (int)pack_mode, fold2_off,
-                          (int)fold2_len, (int)fold2_nrep, (int)fold2_stride, cur_stream()),
+                          (int)fold2_len, (int)fold2_nrep, (int)fold2_stride, lrt, lr_len, cur_stream()),
             "adam_flat");
 }
 
@@ -253,9 +255,11 @@ void sgd_flat(const at::Tensor& p, const at::Tensor& g, const at::Tensor& buf, d
               double dampening, double wd, bool nesterov, double grad_scale, const at::Tensor& step,
               const at::Tensor& arrive, int64_t bump, int64_t pack_off, const OptT& pack_dst, int64_t fold_off,
               int64_t fold_len, int64_t fold_nrep, int64_t fold_stride, int64_t pack_mode, int64_t fold2_off,
-              int64_t fold2_len, int64_t fold2_nrep, int64_t fold2_stride) {
+              int64_t fold2_len, int64_t fold2_nrep, int64_t fold2_stride, const OptT& lr_tab) {
   const int64_t n = p.numel();
   check_cuda(p, "params", F32);
+  int lr_len = 0;
+  const float* lrt = pde::lr_table(lr_tab, p, &lr_len);
   check_cuda(g, "grads", F32, n);
   check_cuda(buf, "momentum_buffer", F32, momentum != 0.0 ? n : 0);
   if (fold_off >= 0 && fold_nrep > 1)
@@ -277,7 +281,7 @@ void sgd_flat(const at::Tensor& p, const at::Tensor& g, const at::Tensor& buf, d
                          (float)dampening, (float)wd, nesterov ? 1 : 0, (float)grad_scale, ptr<long long>(step),
                          ptr<unsigned>(arrive), (int)bump, pd ? pack_off : -1, pd, fold_off, (int)fold_len,
                          (int)fold_nrep, (int)fold_stride, (int)pack_mode, fold2_off, (int)fold2_len,
-                         (int)fold2_nrep, (int)fold2_stride, cur_stream()),
+                         (int)fold2_nrep, (int)fold2_stride, lrt, lr_len, cur_stream()),
             "sgd_flat");
 }
 
@@ -627,13 +631,13 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("fold_off") = -1, py::arg("fold_len") = 0, py::arg("fold_nrep") = 1, py::arg("fold_stride") = 0,
         py::arg("peer_dev") = py::none(), py::arg("ar_off") = 0, py::arg("ar_epoch") = py::none(),
         py::arg("ar_two") = 0, py::arg("pack_mode") = 1, py::arg("fold2_off") = -1, py::arg("fold2_len") = 0,
-        py::arg("fold2_nrep") = 1, py::arg("fold2_stride") = 0);
+        py::arg("fold2_nrep") = 1, py::arg("fold2_stride") = 0, py::arg("lr_table") = py::none());
   m.def("sgd_flat", &sgd_flat, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("lr"), py::arg("momentum"),
         py::arg("dampening"), py::arg("wd"), py::arg("nesterov"), py::arg("grad_scale"), py::arg("step"),
         py::arg("arrive"), py::arg("bump"), py::arg("pack_off") = -1, py::arg("pack_dst") = py::none(),
         py::arg("fold_off") = -1, py::arg("fold_len") = 0, py::arg("fold_nrep") = 1, py::arg("fold_stride") = 0,
         py::arg("pack_mode") = 1, py::arg("fold2_off") = -1, py::arg("fold2_len") = 0, py::arg("fold2_nrep") = 1,
-        py::arg("fold2_stride") = 0);
+        py::arg("fold2_stride") = 0, py::arg("lr_table") = py::none());
   m.def("lenet_pack_w2", &lenet_pack_w2);
   m.def("lenet_pack_w2_v2", &lenet_pack_w2_v2);
   m.def("lenet_conv_fwd2", &lenet_conv_fwd2, py::arg("Xb"), py::arg("B"), py::arg("w1"), py::arg("b1"), py::arg("Wp"),

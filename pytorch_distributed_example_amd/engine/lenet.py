@@ -44,7 +44,8 @@ C2_STRIDE = 25088     # slab: conv2.weight [25000] | pad | conv2.bias [50] at 25
 class LeNetTrainStep:
     def __init__(self, net: torch.nn.Module, batch_size: int = 128, lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 0.0, optimizer: str = "adam", momentum: float = 0.0,
-                 comm=None, overlap: bool = True, force_comm: bool = False, v2: Optional[bool] = None):
+                 comm=None, overlap: bool = True, force_comm: bool = False, v2: Optional[bool] = None,
+                 lr_schedule=None):
         self.net = net
         p0 = next(net.parameters())
         if not p0.is_cuda:
@@ -192,6 +193,36 @@ class LeNetTrainStep:
         self.nbatches = 0
         self.graphs = {}
         self.bwd_dbg = 0          # ablation switch of the v2 conv backward (tools/lenet_phases.py only)
+        # learning-rate schedule: a device table of one fp32 rate per optimizer step, indexed inside the
+        # optimizer kernel by counters[0] (optim.lr_scheduler); None = the by-value self.lr
+        self.lr_table = None
+        self._lr_host = None
+        if lr_schedule is not None:
+            self.set_lr_table(lr_schedule)
+
+    # ------------------------------------------------------------------ learning-rate schedule
+    def set_lr_table(self, table):
+        """Attach a per-step learning-rate table (a sequence of rates, or an fp32 tensor on the training
+        device); ``None`` detaches.  Optimizer step t (1-based, ``counters[0]``) then uses
+        ``table[min(t-1, len-1)]`` in eager steps and in every graph replay, whatever its step count,
+        and ``self.lr`` is ignored.  Captured graphs hold the table's address: they are dropped here."""
+        from ..optim.lr_scheduler import check_table, make_table
+        if table is not None:
+            table = (check_table(table, self.device, "LeNetTrainStep") if isinstance(table, torch.Tensor)
+                     else make_table(table, self.device))
+        self.lr_table = table
+        self._lr_host = None if table is None else table.cpu()
+        self.graphs.clear()
+
+    def lr_step_count(self) -> int:
+        """Optimizer steps taken so far (reads the device counter: a host sync)."""
+        return int(self.counters[0].item())
+
+    def current_lr(self) -> float:
+        """The learning rate the next optimizer step uses."""
+        if self._lr_host is None:
+            return self.lr
+        return float(self._lr_host[min(self.lr_step_count(), self._lr_host.numel() - 1)])
 
     # ------------------------------------------------------------------ data binding
     def bind_dataset(self, images: torch.Tensor, labels: torch.Tensor):
@@ -243,10 +274,11 @@ class LeNetTrainStep:
                            ar_epoch=self.ar_epoch, ar_two=int(fuse_ar == "adam2"))
             K.adam_flat(self.params[sl], self.grads[sl], self.m[sl], self.v[sl], self.lr, self.betas[0],
                         self.betas[1], self.eps, self.wd, False, scale, self.counters, self.arrive, -1, pack_off,
-                        pack, pack_mode=mode, **folds, **far)
+                        pack, pack_mode=mode, lr_table=self.lr_table, **folds, **far)
         else:
             K.sgd_flat(self.params[sl], self.grads[sl], self.m[sl], self.lr, self.momentum, 0.0, self.wd, False,
-                       scale, self.counters, self.arrive, -1, pack_off, pack, pack_mode=mode, **folds)
+                       scale, self.counters, self.arrive, -1, pack_off, pack, pack_mode=mode, lr_table=self.lr_table,
+                       **folds)
 
     def _fold_ar(self, B: int, two: bool = False):
         """The "serial ...:pfold" / "pfold2" routes: the ext-mode conv-gradient fold and the in-place
@@ -570,9 +602,10 @@ class LeNetTrainStep:
             elif self.momentum:
                 st["momentum_buffer"] = self.layout.view(self.m, n).detach().clone()
             state[i] = st
-        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd, "amsgrad": False,
+        lr = self.current_lr()
+        group = {"lr": lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd, "amsgrad": False,
                  "params": list(range(len(names)))} if self.optimizer == "adam" else {
-            "lr": self.lr, "momentum": self.momentum, "weight_decay": self.wd, "dampening": 0.0,
+            "lr": lr, "momentum": self.momentum, "weight_decay": self.wd, "dampening": 0.0,
             "nesterov": False, "params": list(range(len(names)))}
         return {"state": state, "param_groups": [group]}
 
@@ -654,6 +687,8 @@ class LeNetTrainStep:
         if not self.comm_on:
             return {}
         cands = candidates or self.schedule_candidates()
+        # counters[0] is also the index into an attached learning-rate table: restoring it restores the
+        # schedule position, so the trial steps do not consume the schedule
         state = [self.params, self.m, self.counters, self.Xb, self.Yb, self.rowsb] + (
             [self.v] if self.v is not self.m else [])
         snap = [t.clone() for t in state]

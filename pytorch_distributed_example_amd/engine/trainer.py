@@ -75,7 +75,7 @@ def _loss_fn(output, label):
 
 class Trainer(object):
     def __init__(self, net, optimizer, train_loader, test_loader, device, distributed, do_eval,
-                 manual_average: bool = False, autocast_dtype=None):
+                 manual_average: bool = False, autocast_dtype=None, scheduler=None):
         self.net = net
         self.optimizer = optimizer
         self.train_loader = train_loader
@@ -87,6 +87,7 @@ class Trainer(object):
         # mixed precision (``--dtype bf16``): forward + loss under torch.autocast, fp32 parameters,
         # gradients and optimizer state (the loss itself is computed from fp32 logits)
         self.autocast_dtype = autocast_dtype
+        self.scheduler = scheduler              # optional lr scheduler: step() once per optimizer step
         self.printer = print
 
     def _forward(self, data, label):
@@ -136,6 +137,8 @@ class Trainer(object):
                     self.average_gradients()
             with prof.range("optimizer"):
                 self.optimizer.step()
+            if self.scheduler is not None:
+                self.scheduler.step()
 
             train_loss.update(loss, data.size(0))
             train_acc.update(output, label)
@@ -171,7 +174,8 @@ class Trainer(object):
 class FusedTrainer(object):
     """Same interface/prints as ``Trainer`` over the fused LeNet engine."""
 
-    def __init__(self, engine, train_set, test_set, sampler, do_eval, use_graph: bool = True, set_epoch=False):
+    def __init__(self, engine, train_set, test_set, sampler, do_eval, use_graph: bool = True, set_epoch=False,
+                 scheduler=None):
         self.engine = engine
         self.train_set = train_set
         self.test_set = test_set
@@ -179,6 +183,7 @@ class FusedTrainer(object):
         self.do_eval = do_eval
         self.use_graph = use_graph
         self.set_epoch = set_epoch
+        self.scheduler = scheduler              # optional optim.lr_scheduler.LRTable attached to the engine
         self.printer = print
         engine.bind_dataset(train_set.images, train_set.labels)
 
@@ -212,6 +217,8 @@ class FusedTrainer(object):
     def train(self):
         self.engine.set_epoch_indices(self.sampler.indices_tensor())
         self.engine.run_epoch(use_graph=self.use_graph)
+        if self.scheduler is not None:           # the kernels followed the table; the host's view catches up
+            self.scheduler.step(self.engine.nbatches)
         loss_sum, correct, n = self.engine.read_meters()     # synchronises: the epoch's comm is done
         self.check_comm_health()
         a, acc = Average(), Accuracy()

@@ -10,6 +10,11 @@ The classes subclass ``torch.optim.Optimizer`` so ``state_dict()`` / ``load_stat
 torch's format (``state[i] = {step, exp_avg, exp_avg_sq}`` / ``{momentum_buffer}``): per-parameter
 state entries are views into the flat buffers.  CPU parameters (the reference's ``--no-cuda``
 path) use the same math with ATen CPU ops.
+
+Learning-rate schedules: ``set_lr_table`` attaches one device table of per-step rates per group
+(``optim.lr_scheduler``); the kernel then reads the rate of step t from the table with its device
+step count and ignores ``group["lr"]``, so a captured step follows the schedule.  The CPU paths keep
+reading ``group["lr"]`` (which ``LRTable.step()`` writes).
 """
 from __future__ import annotations
 
@@ -80,6 +85,29 @@ class _FusedBase(torch.optim.Optimizer):
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._flat = {}
+        self._lr_tables = [None] * len(self.param_groups)
+
+    def set_lr_table(self, tables):
+        """Attach per-step learning-rate tables (fp32 tensors on the groups' devices): one per group, or
+        one shared by all; ``None`` detaches.  GPU groups then ignore ``group["lr"]``: step t uses
+        ``table[min(t-1, len-1)]``."""
+        from .lr_scheduler import per_group_tables
+        devices = [g["params"][0].device for g in self.param_groups]
+        self._lr_tables = per_group_tables(tables, len(self.param_groups), devices, type(self).__name__)
+
+    def _lr_table(self, gi):
+        return self._lr_tables[gi] if gi < len(self._lr_tables) else None
+
+    def lr_step_count(self):
+        """Optimizer steps taken so far (the device count of the first group: a host sync)."""
+        for gi, group in enumerate(self.param_groups):
+            if gi in self._flat:
+                return int(self._flat[gi].step_ctr.item())
+            for p in group["params"]:
+                st = self.state.get(p)
+                if st and "step" in st:
+                    return int(float(st["step"]))
+        return None
 
     def _gpu_group(self, group) -> bool:
         ps = group["params"]
@@ -168,7 +196,7 @@ class Adam(_FusedBase):
                 frozen = _Frozen(fg, missing) if (missing := fg.sync_grads(group["params"])) else None
                 kernels().adam_flat(fg.params, fg.grads, fg.bufs["exp_avg"], fg.bufs["exp_avg_sq"], group["lr"], b1,
                                     b2, group["eps"], group["weight_decay"], group["decoupled_weight_decay"],
-                                    self.grad_scale, fg.step_ctr, fg.arrive, 1)
+                                    self.grad_scale, fg.step_ctr, fg.arrive, 1, lr_table=self._lr_table(gi))
                 if frozen is not None:
                     frozen.restore()
                 self._after_step(gi, group)
@@ -204,7 +232,7 @@ class SGD(_FusedBase):
                 frozen = _Frozen(fg, missing) if (missing := fg.sync_grads(group["params"])) else None
                 kernels().sgd_flat(fg.params, fg.grads, fg.bufs["momentum_buffer"], group["lr"], group["momentum"],
                                    group["dampening"], group["weight_decay"], group["nesterov"], self.grad_scale,
-                                   fg.step_ctr, fg.arrive, 1)
+                                   fg.step_ctr, fg.arrive, 1, lr_table=self._lr_table(gi))
                 if frozen is not None:
                     frozen.restore()
                 self._after_step(gi, group)

@@ -13,6 +13,11 @@ one streaming pass with no host synchronisation:
 Per-group weight decay is a per-64-element flag table (every parameter starts on a 64-element
 boundary of the flat layout).  State is exposed in torch.optim's ``state_dict`` layout
 (exp_avg / exp_avg_sq / momentum_buffer / step per parameter) plus ``master`` (fp32 weights).
+
+Learning-rate schedules: ``set_lr_table`` attaches one device table of per-step rates
+(``optim.lr_scheduler``; one table, the groups share every hyper-parameter but weight decay).  The
+kernel reads the rate of step t from it -- with ``capturable=True`` from the device step count, so a
+captured step follows the schedule on replay -- and ignores ``group["lr"]``.
 """
 from __future__ import annotations
 
@@ -32,6 +37,7 @@ class _MasterBase(torch.optim.Optimizer):
         self.grad_scale = grad_scale
         self._flat = None
         self._step = 0
+        self._lr_table = None
         hp = {tuple((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in g.items()
                     if k not in ("params", "weight_decay")) for g in self.param_groups}
         if len(hp) != 1:
@@ -40,6 +46,24 @@ class _MasterBase(torch.optim.Optimizer):
 
     def _all_params(self):
         return [p for g in self.param_groups for p in g["params"]]
+
+    def set_lr_table(self, table):
+        """Attach a per-step learning-rate table (fp32, on the parameters' device; a list with the same
+        table for every group is accepted too); ``None`` detaches.  Step t then uses
+        ``table[min(t-1, len-1)]`` and ``group["lr"]`` is ignored."""
+        from .lr_scheduler import per_group_tables
+        devices = [g["params"][0].device for g in self.param_groups]
+        tabs = per_group_tables(table, len(self.param_groups), devices, type(self).__name__)
+        if any(t is not tabs[0] and not torch.equal(t, tabs[0]) for t in tabs[1:]):
+            raise ValueError(f"{type(self).__name__}: one learning-rate table for all groups (hyper-parameters "
+                             "other than weight_decay must be equal across groups)")
+        self._lr_table = tabs[0]
+
+    def lr_step_count(self):
+        """Optimizer steps taken so far (capturable: the device count, a host sync)."""
+        if self.capturable and self._flat is not None:
+            return int(self._flat["step_dev"].item())
+        return self._step
 
     def _build(self):
         params = self._all_params()
@@ -72,7 +96,8 @@ class _MasterBase(torch.optim.Optimizer):
             bufs[k] = torch.zeros(n, device=dev, dtype=torch.float32)
         self._flat = dict(layout=layout, p=fp, g=fg, bufs=bufs, decay=decay.to(dev),
                           sumsq=torch.zeros(1025, device=dev, dtype=torch.float32),   # [0] + partials
-                          step_dev=torch.full((1,), float(self._step), device=dev, dtype=torch.float32))
+                          step_dev=torch.full((1,), float(self._step), device=dev, dtype=torch.float32),
+                          arrive=torch.zeros(1, device=dev, dtype=torch.int32))   # SGDMaster's step fan-in
         for p in params:
             st = self.state[p]
             name = p._pde_flat[3]
@@ -179,7 +204,8 @@ class AdamWMaster(_MasterBase):
         b1, b2 = g0["betas"]
         K.adamw_master(f["bufs"]["master"], f["p"], f["g"], f["bufs"]["exp_avg"], f["bufs"]["exp_avg_sq"], g0["lr"],
                        b1, b2, g0["eps"], self._wd, self.grad_scale, self._step, f["decay"], clip,
-                       float(self.max_grad_norm or 1.0), f["step_dev"] if self.capturable else None)
+                       float(self.max_grad_norm or 1.0), f["step_dev"] if self.capturable else None,
+                       lr_table=self._lr_table)
 
     def grad_norm(self) -> float:
         """Global grad norm of the last clipped step (host sync; for logging only)."""
@@ -189,12 +215,19 @@ class AdamWMaster(_MasterBase):
 class SGDMaster(_MasterBase):
     _state_keys = ("momentum_buffer",)
 
-    def __init__(self, params, lr=0.1, momentum=0.9, weight_decay=0.0, nesterov=False, grad_scale: float = 1.0):
+    def __init__(self, params, lr=0.1, momentum=0.9, weight_decay=0.0, nesterov=False, grad_scale: float = 1.0,
+                 capturable: bool = False):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov),
                          grad_scale)
+        # capturable: as in AdamWMaster, the step count is a device tensor advanced in stream order (by
+        # the kernel's last-arriving block, so a graph replay counts); SGD's update needs no step, the
+        # count only selects the entry of an attached learning-rate table
+        self.capturable = capturable
 
     def _kernel(self):
         f = self._flat
         g0 = self.param_groups[0]
         kernels().sgd_master(f["bufs"]["master"], f["p"], f["g"], f["bufs"]["momentum_buffer"], g0["lr"],
-                             g0["momentum"], self._wd, g0["nesterov"], self.grad_scale, f["decay"])
+                             g0["momentum"], self._wd, g0["nesterov"], self.grad_scale, f["decay"],
+                             step=self._step, step_dev=f["step_dev"] if self.capturable else None,
+                             arrive=f["arrive"] if self.capturable else None, lr_table=self._lr_table)

@@ -17,7 +17,9 @@ reference's always-on cProfile wrapper; --no-cprofile turns it off), --metrics P
 --log-rank0-only, --no-graph, --set-epoch, --bucket-mb (DDP gradient bucket cap, autograd engine),
 --dtype {fp32,bf16} (bf16: torch.autocast mixed precision over the ATen layer path with fp32
 parameters, gradients and optimizer state; the fused engine and the framework's toy-CNN kernels are
-fp32, the reference's dtype).
+fp32, the reference's dtype), --lr-schedule {constant,step,cosine} with --lr-warmup / --lr-step-size /
+--lr-gamma / --lr-min (a per-step table over epochs x batches-per-epoch steps, built identically on
+every rank and read on the device by the optimizer kernels, so hipGraph replays follow it).
 """
 import argparse
 import cProfile
@@ -36,7 +38,7 @@ from pytorch_distributed_example_amd.data import (DeviceDataLoader, DistributedS
 from pytorch_distributed_example_amd.engine import LeNetTrainStep  # noqa: E402
 from pytorch_distributed_example_amd.engine.trainer import FusedTrainer, Trainer  # noqa: E402
 from pytorch_distributed_example_amd.models import MLP, build_net  # noqa: E402
-from pytorch_distributed_example_amd.optim import SGD, Adam  # noqa: E402
+from pytorch_distributed_example_amd.optim import SGD, Adam, LRTable, lr_scheduler  # noqa: E402
 from pytorch_distributed_example_amd.parallel import DistributedDataParallel  # noqa: E402
 from pytorch_distributed_example_amd.utils.checkpoint import load_checkpoint, save_checkpoint  # noqa: E402
 
@@ -78,6 +80,7 @@ class _Printer:
         self.metrics = open(metrics_path, "a") if metrics_path else None
         self.t0 = time.perf_counter()
         self.images = images_per_epoch
+        self.lr_fn = None            # set when a schedule other than "constant" is on: rows gain "lr"
 
     def __call__(self, *parts):
         if self.enabled:
@@ -85,10 +88,29 @@ class _Printer:
         if self.metrics is not None:
             now = time.perf_counter()
             line = " ".join(parts)
-            self.metrics.write(json.dumps({"line": line, "epoch_time_s": now - self.t0,
-                                           "images_per_s": self.images / max(1e-9, now - self.t0)}) + "\n")
+            row = {"line": line, "epoch_time_s": now - self.t0,
+                   "images_per_s": self.images / max(1e-9, now - self.t0)}
+            if self.lr_fn is not None:
+                row["lr"] = self.lr_fn()
+            self.metrics.write(json.dumps(row) + "\n")
             self.metrics.flush()
             self.t0 = now
+
+
+def schedule_lrs(args, steps_per_epoch):
+    """The per-step learning-rate list of --lr-schedule over epochs x batches-per-epoch optimizer steps
+    (None for "constant"); the same arguments give the same list on every rank."""
+    total = max(1, args.epochs * steps_per_epoch)
+    base = args.learning_rate
+    if args.lr_schedule == "cosine":
+        return lr_scheduler.warmup_cosine(base, min(args.lr_warmup, total), total, args.lr_min)
+    if args.lr_schedule == "step":
+        lrs = lr_scheduler.step_decay(base, args.lr_step_size or steps_per_epoch, args.lr_gamma, total)
+        if args.lr_warmup:
+            w = min(args.lr_warmup, total)
+            lrs = [lr * (k + 1) / w if k < w else lr for k, lr in enumerate(lrs)]
+        return lrs
+    return None
 
 
 def run(args):
@@ -128,6 +150,8 @@ def run(args):
         payload = load_checkpoint(args.resume, net)
         start_epoch = int(payload.get("epoch", 0))
 
+    lrs = schedule_lrs(args, len(train_loader))
+    scheduler = None
     if engine == "fused":
         comm = dist.engine_comm() if distributed else None
         eng = LeNetTrainStep(net, batch_size=args.batch_size, lr=args.learning_rate, optimizer=args.optimizer,
@@ -135,8 +159,10 @@ def run(args):
         if payload is not None and "optimizer" in payload:
             eng.load_optimizer_state_dict(payload["optimizer"])
         eng.sync_params()
+        if lrs is not None:
+            scheduler = LRTable(eng, lrs)
         trainer = FusedTrainer(eng, train_loader.dataset, test_loader.dataset, train_loader.sampler, args.eval,
-                               use_graph=not args.no_graph, set_epoch=args.set_epoch)
+                               use_graph=not args.no_graph, set_epoch=args.set_epoch, scheduler=scheduler)
         opt_state = eng.optimizer_state_dict
     else:
         model = net
@@ -147,12 +173,22 @@ def run(args):
                      else SGD(params, lr=args.learning_rate, momentum=0.9))
         if payload is not None and "optimizer" in payload:
             optimizer.load_state_dict(payload["optimizer"])
+        if lrs is not None:
+            scheduler = LRTable(optimizer, lrs)
         trainer = Trainer(model, optimizer, train_loader, test_loader, device, distributed, args.eval,
                           manual_average=(args.ddp == "off"),
-                          autocast_dtype=torch.bfloat16 if args.dtype == "bf16" else None)
+                          autocast_dtype=torch.bfloat16 if args.dtype == "bf16" else None, scheduler=scheduler)
         trainer.set_epoch = args.set_epoch
         opt_state = optimizer.state_dict
     trainer.printer = printer
+    if scheduler is not None:
+        # resume: the table is rebuilt from the arguments; the checkpoint restores the host's position and
+        # the restored optimizer step count selects the entry the kernels continue from
+        sd = (payload or {}).get("extra", {}).get("lr_scheduler")
+        if sd is not None:          # position only: this run's --epochs decides the table's length
+            scheduler.load_state_dict({"last_epoch": sd["last_epoch"]})
+        # metrics rows: the rate of the last optimizer step taken (entry steps-1 of the table)
+        printer.lr_fn = lambda: scheduler.lr_at(scheduler.last_epoch - 1)[0]
 
     epochs = args.epochs
     # resume: epochs start_epoch+1..E, numbered (and --set-epoch seeded) as in an uninterrupted run
@@ -160,7 +196,8 @@ def run(args):
     if engine == "fused":
         trainer.check_comm_health()        # never checkpoint replicas a failed all-reduce let diverge
     if args.save:
-        save_checkpoint(args.save, net, opt_state(), epoch=epochs, rank=rank)
+        extra = {"lr_scheduler": scheduler.state_dict()} if scheduler is not None else None
+        save_checkpoint(args.save, net, opt_state(), epoch=epochs, extra=extra, rank=rank)
 
 
 def init_process(args):
@@ -208,6 +245,13 @@ def build_parser():
                              'own one- / two-bucket schedules)')
     parser.add_argument('--dtype', choices=['fp32', 'bf16'], default='fp32',
                         help='compute dtype: bf16 = autocast mixed precision (fp32 params / grads / Adam state)')
+    parser.add_argument('--lr-schedule', choices=['constant', 'step', 'cosine'], default='constant',
+                        help='per-step learning-rate schedule over epochs x batches-per-epoch steps')
+    parser.add_argument('--lr-warmup', type=int, default=0, help='linear warm-up steps (step / cosine)')
+    parser.add_argument('--lr-step-size', type=int, default=0,
+                        help='step schedule: steps between decays (0 = one epoch)')
+    parser.add_argument('--lr-gamma', type=float, default=0.1, help='step schedule: decay factor')
+    parser.add_argument('--lr-min', type=float, default=0.0, help='cosine schedule: final learning rate')
     return parser
 
 
