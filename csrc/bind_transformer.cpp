@@ -6,8 +6,47 @@
 namespace pde {
 namespace {
 
+// Dropout site of a launch (pde_kernels.h PdeDrop).  rng = None: no dropout.  Otherwise the 4-word int32
+// snapshot of ops/rng.py DeviceRNG.next(), the site number (16 bits), the integer threshold (32 bits at
+// elementwise sites, 8 at attention sites) and 1 / keep.
+PdeDrop drop_of(const OptT& rng, int64_t site, int64_t thr, double inv_keep, int thr_bits = 32) {
+  PdeDrop d{nullptr, 0u, 0u, 1.f};
+  if (!rng.has_value() || !rng->defined()) return d;
+  check_cuda(*rng, "rng snapshot", I32, 4);
+  TORCH_CHECK(rng->numel() == 4, "rng snapshot must hold 4 words");
+  TORCH_CHECK(site >= 0 && site < 65536, "dropout site must fit 16 bits, got ", site);
+  TORCH_CHECK(thr >= 0 && thr < (int64_t(1) << thr_bits), "dropout threshold out of range: ", thr);
+  TORCH_CHECK(inv_keep >= 1.0, "dropout 1/keep must be >= 1, got ", inv_keep);
+  d.rng = reinterpret_cast<const uint32_t*>(rng->data_ptr());
+  d.site = (uint32_t)site;
+  d.thr = (uint32_t)thr;
+  d.inv_keep = (float)inv_keep;
+  return d;
+}
+
+void rng_next(const at::Tensor& state, const at::Tensor& snap) {
+  check_cuda(state, "state", I32, 4);
+  check_cuda(snap, "snapshot", I32, 4);
+  TORCH_CHECK(state.numel() == 4 && snap.numel() == 4, "rng state and snapshot hold 4 words");
+  hip_check(pde_rng_next(ptr<uint32_t>(state), ptr<uint32_t>(snap), cur_stream()), "rng_next");
+}
+
+// debug / tests: out (uint8, any shape; attention: [B, H, T, T]) = keep-mask of the site
+void dropout_mask(const at::Tensor& rng, int64_t site, int64_t thr, const at::Tensor& out, bool attention) {
+  const PdeDrop d = drop_of(rng, site, thr, 1.0, attention ? 8 : 32);
+  check_cuda(out, "out", U8);
+  int T = 0;
+  if (attention) {
+    TORCH_CHECK(out.dim() == 4 && out.size(2) == out.size(3) && out.size(2) % 4 == 0,
+                "attention mask must be [B, H, T, T] with T % 4 == 0");
+    T = (int)out.size(2);
+  }
+  hip_check(pde_dropout_mask(d.rng, d.site, d.thr, ptr<uint8_t>(out), out.numel(), T, cur_stream()), "dropout_mask");
+}
+
 void ln_fwd(const at::Tensor& X, const at::Tensor& G, const at::Tensor& B, const at::Tensor& Y,
-            const at::Tensor& mean, const at::Tensor& rstd, double eps, const OptT& D, const OptT& S) {
+            const at::Tensor& mean, const at::Tensor& rstd, double eps, const OptT& D, const OptT& S,
+            const OptT& rng, int64_t site, int64_t thr, double inv_keep) {
   const int64_t C = X.size(-1), N = X.numel() / C;
   TORCH_CHECK(C % 4 == 0 && C <= 2048, "ln: C must be a multiple of 4 and <= 2048");
   check_cuda(X, "X", BF16);
@@ -19,8 +58,10 @@ void ln_fwd(const at::Tensor& X, const at::Tensor& G, const at::Tensor& B, const
   const void* dp = optr<void>(D, "D", BF16, N * C);
   void* sp = optr<void>(S, "S", BF16, N * C);
   TORCH_CHECK((dp == nullptr) == (sp == nullptr), "ln_fwd: D (residual input) and S (sum output) go together");
+  const PdeDrop drop = drop_of(rng, site, thr, inv_keep);
+  TORCH_CHECK(drop.rng == nullptr || dp != nullptr, "ln_fwd: dropout acts on the residual input D");
   hip_check(pde_ln_fwd(X.data_ptr(), dp, sp, G.data_ptr(), B.data_ptr(), Y.data_ptr(), ptr<float>(mean), ptr<float>(rstd),
-                       (int)N, (int)C, (float)eps, cur_stream()),
+                       (int)N, (int)C, (float)eps, drop, cur_stream()),
             "ln_fwd");
 }
 
@@ -28,7 +69,8 @@ int64_t ln_bwd_blocks(int64_t N) { return pde_ln_bwd_blocks((int)N); }
 
 void ln_bwd(const at::Tensor& dY, const at::Tensor& X, const at::Tensor& mean, const at::Tensor& rstd,
             const at::Tensor& G, const OptT& dRes, const at::Tensor& dX, const at::Tensor& part, const at::Tensor& dG,
-            const at::Tensor& dB, bool accumulate) {
+            const at::Tensor& dB, bool accumulate, const OptT& dD, const OptT& rng, int64_t site, int64_t thr,
+            double inv_keep) {
   const int64_t C = X.size(-1), N = X.numel() / C;
   TORCH_CHECK(C % 4 == 0 && C <= 2048, "ln: C must be a multiple of 4 and <= 2048");
   check_cuda(dY, "dY", BF16, N * C);
@@ -41,9 +83,12 @@ void ln_bwd(const at::Tensor& dY, const at::Tensor& X, const at::Tensor& mean, c
   check_cuda(dG, "dgamma", BF16, C);
   check_cuda(dB, "dbeta", BF16, C);
   const void* dr = optr<at::BFloat16>(dRes, "dRes", BF16, N * C);
+  void* dd = optr<void>(dD, "dD", BF16, N * C);
+  const PdeDrop drop = drop_of(rng, site, thr, inv_keep);
+  TORCH_CHECK((drop.rng != nullptr) == (dd != nullptr), "ln_bwd: dD (gradient of the dropped summand) goes with rng");
   hip_check(pde_ln_bwd(dY.data_ptr(), X.data_ptr(), ptr<float>(mean), ptr<float>(rstd), G.data_ptr(), dr,
                        dX.data_ptr(), ptr<float>(part), dG.data_ptr(), dB.data_ptr(), (int)N, (int)C, accumulate,
-                       cur_stream()),
+                       drop, dd, cur_stream()),
             "ln_bwd");
 }
 
@@ -85,7 +130,8 @@ void xent_bf16(const at::Tensor& logits, const at::Tensor& tgt, int64_t V, doubl
             "xent_bf16");
 }
 
-void embed_fwd(const at::Tensor& idx, const at::Tensor& wte, const at::Tensor& wpe, const at::Tensor& out, int64_t T) {
+void embed_fwd(const at::Tensor& idx, const at::Tensor& wte, const at::Tensor& wpe, const at::Tensor& out, int64_t T,
+               const OptT& rng, int64_t site, int64_t thr, double inv_keep) {
   check_cuda(idx, "idx", I64);
   const int64_t N = idx.numel(), C = wte.size(1);
   TORCH_CHECK(C % 4 == 0 && N % T == 0 && wpe.size(0) >= T, "embed: bad shapes");
@@ -93,21 +139,24 @@ void embed_fwd(const at::Tensor& idx, const at::Tensor& wte, const at::Tensor& w
   check_cuda(wpe, "wpe", BF16);
   check_cuda(out, "out", BF16, N * C);
   hip_check(pde_embed_fwd(ptr<int64_t>(idx), wte.data_ptr(), wpe.data_ptr(), out.data_ptr(), (int)N, (int)T, (int)C,
-                          cur_stream()),
+                          drop_of(rng, site, thr, inv_keep), cur_stream()),
             "embed_fwd");
 }
 
 void embed_bwd(const at::Tensor& dX, const at::Tensor& idx, const at::Tensor& dwte, const at::Tensor& dwpe,
-               const at::Tensor& acc, const at::Tensor& touched, int64_t T, bool accumulate_pos) {
+               const at::Tensor& acc, const at::Tensor& touched, int64_t T, bool accumulate_pos, const OptT& rng,
+               int64_t site, int64_t thr, double inv_keep) {
   check_cuda(idx, "idx", I64);
   const int64_t N = idx.numel(), C = dwte.size(1), Vp = dwte.size(0);
+  TORCH_CHECK(C % 4 == 0, "embed: C must be a multiple of 4");
   check_cuda(dX, "dX", BF16, N * C);
   check_cuda(dwte, "dwte", BF16);
   check_cuda(dwpe, "dwpe", BF16, T * C);
   check_cuda(acc, "acc", F32, Vp * C);
   check_cuda(touched, "touched", U8, Vp);
   hip_check(pde_embed_bwd(dX.data_ptr(), ptr<int64_t>(idx), dwte.data_ptr(), dwpe.data_ptr(), ptr<float>(acc),
-                          ptr<uint8_t>(touched), (int)N, (int)T, (int)C, (int)Vp, accumulate_pos, cur_stream()),
+                          ptr<uint8_t>(touched), (int)N, (int)T, (int)C, (int)Vp, accumulate_pos,
+                          drop_of(rng, site, thr, inv_keep), cur_stream()),
             "embed_bwd");
 }
 
@@ -199,7 +248,8 @@ void check_qkv(const at::Tensor& t, const char* name, int64_t B, int64_t T, int6
 }
 
 void attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
-              const at::Tensor& lse, int64_t H, double scale) {
+              const at::Tensor& lse, int64_t H, double scale, const OptT& rng, int64_t site, int64_t thr,
+              double inv_keep) {
   const int64_t B = q.size(0), T = q.size(1);
   TORCH_CHECK(T % 128 == 0, "attention: T must be a multiple of 128");
   check_qkv(q, "q", B, T, H);
@@ -209,13 +259,15 @@ void attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, con
   check_qkv(o, "o", B, T, H);
   check_cuda(lse, "lse", F32, B * H * T);
   hip_check(pde_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), (int)q.stride(1), o.data_ptr(), (int)o.stride(1),
-                         ptr<float>(lse), (int)B, (int)T, (int)H, (float)scale, cur_stream()),
+                         ptr<float>(lse), (int)B, (int)T, (int)H, (float)scale, drop_of(rng, site, thr, inv_keep, 8),
+                         cur_stream()),
             "attn_fwd");
 }
 
 void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
               const at::Tensor& dout, const at::Tensor& lse, const at::Tensor& Dd, const at::Tensor& dq,
-              const at::Tensor& dk, const at::Tensor& dv, int64_t H, double scale) {
+              const at::Tensor& dk, const at::Tensor& dv, int64_t H, double scale, const OptT& rng, int64_t site,
+              int64_t thr, double inv_keep) {
   const int64_t B = q.size(0), T = q.size(1);
   TORCH_CHECK(T % 128 == 0, "attention: T must be a multiple of 128");
   for (auto* p : {&q, &k, &v, &dq, &dk, &dv}) check_qkv(*p, "q/k/v/dq/dk/dv", B, T, H);
@@ -228,7 +280,8 @@ void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, con
   check_cuda(Dd, "D", F32, B * H * T);
   hip_check(pde_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), (int)q.stride(1), o.data_ptr(), dout.data_ptr(),
                          (int)o.stride(1), ptr<float>(lse), ptr<float>(Dd), dq.data_ptr(), dk.data_ptr(),
-                         dv.data_ptr(), (int)B, (int)T, (int)H, (float)scale, cur_stream()),
+                         dv.data_ptr(), (int)B, (int)T, (int)H, (float)scale, drop_of(rng, site, thr, inv_keep, 8),
+                         cur_stream()),
             "attn_bwd");
 }
 
@@ -284,9 +337,13 @@ int64_t gemm_num_cfgs() { return pde_gemm_num_cfgs(); }
 void register_transformer(pybind11::module& m) {
   namespace py = pybind11;
   m.def("ln_fwd", &ln_fwd, py::arg("X"), py::arg("G"), py::arg("B"), py::arg("Y"), py::arg("mean"), py::arg("rstd"),
-        py::arg("eps"), py::arg("D") = py::none(), py::arg("S") = py::none());
+        py::arg("eps"), py::arg("D") = py::none(), py::arg("S") = py::none(), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
   m.def("ln_bwd_blocks", &ln_bwd_blocks);
-  m.def("ln_bwd", &ln_bwd);
+  m.def("ln_bwd", &ln_bwd, py::arg("dY"), py::arg("X"), py::arg("mean"), py::arg("rstd"), py::arg("G"), py::arg("dRes"),
+        py::arg("dX"), py::arg("part"), py::arg("dG"), py::arg("dB"), py::arg("accumulate"),
+        py::arg("dD") = py::none(), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
+  m.def("rng_next", &rng_next);
+  m.def("dropout_mask", &dropout_mask);
   m.def("sum_slabs_bf16", &sum_slabs_bf16);
   m.def("gemm_bf16", &gemm, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("ta"), py::arg("tb"), py::arg("epi"),
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"), py::arg("ldb"), py::arg("ldc"), py::arg("splits") = 1,
@@ -301,8 +358,9 @@ void register_transformer(pybind11::module& m) {
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd", &gelu_bwd);
   m.def("xent_bf16", &xent_bf16);
-  m.def("embed_fwd", &embed_fwd);
-  m.def("embed_bwd", &embed_bwd);
+  m.def("embed_fwd", &embed_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe"), py::arg("out"), py::arg("T"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
+  m.def("embed_bwd", &embed_bwd, py::arg("dX"), py::arg("idx"), py::arg("dwte"), py::arg("dwpe"), py::arg("acc"),
+        py::arg("touched"), py::arg("T"), py::arg("accumulate_pos"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
   m.def("sumsq_bf16", &sumsq_bf16, py::arg("g"), py::arg("scale"), py::arg("out"), py::arg("step_inc") = py::none());
   m.def("adamw_master", &adamw_master, py::arg("master"), py::arg("p16"), py::arg("g16"), py::arg("m"), py::arg("v"),
         py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("grad_scale"),
@@ -314,8 +372,10 @@ void register_transformer(pybind11::module& m) {
   m.def("token_batch", &token_batch);
   m.def("colsum_bf16_splits", &colsum_bf16_splits);
   m.def("colsum_bf16", &colsum_bf16);
-  m.def("attn_fwd", &attn_fwd);
-  m.def("attn_bwd", &attn_bwd);
+  m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("H"),
+        py::arg("scale"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
+  m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"), py::arg("lse"),
+        py::arg("D"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("H"), py::arg("scale"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
   m.def("attn_set_variant", [](int64_t v) { pde_attn_set_variant((int)v); });
 }
 

@@ -122,21 +122,38 @@ hipError_t pde_colsum(const float* x, int M, int N, float* out, hipStream_t st);
 hipError_t pde_gather_rows(const float* src, const long long* idx, int n, int row_floats, float* out, hipStream_t st);
 
 
+// ---- dropout (pde_rng.h; rng.hip) ----
+// One dropout site of a launch.  rng = nullptr: no dropout (the launch runs the kernel it ran before
+// dropout existed).  Otherwise rng is the 4-word snapshot {seed lo, seed hi, draw, stream} in device
+// memory, thr the integer threshold (kept iff word >= thr; 32-bit at elementwise sites, 8-bit at
+// attention sites) and inv_keep = 1 / (1 - realised probability).
+typedef struct PdeDrop {
+  const uint32_t* rng;
+  uint32_t site;
+  uint32_t thr;
+  float inv_keep;
+} PdeDrop;
+hipError_t pde_rng_next(uint32_t* state, uint32_t* snapshot, hipStream_t st);
+// debug only: uint8 keep-mask of an elementwise site (n elements) or an attention site ([BH, T, T], n = BH*T*T)
+hipError_t pde_dropout_mask(const uint32_t* rng, uint32_t site, uint32_t thr, uint8_t* out, int64_t n, int attn_T,
+                            hipStream_t st);
+
 // ---- transformer (transformer.hip) ----
+// drop (ln_fwd): s = x + drop(d).  drop (ln_bwd): also writes dD = mask * dX * inv_keep of that site.
 hipError_t pde_ln_fwd(const void* X, const void* D, void* S, const void* G, const void* B, void* Y, float* mean,
-                      float* rstd, int N, int C, float eps, hipStream_t st);
+                      float* rstd, int N, int C, float eps, PdeDrop drop, hipStream_t st);
 int pde_ln_bwd_blocks(int N);
 hipError_t pde_ln_bwd(const void* dY, const void* X, const float* mean, const float* rstd, const void* G,
                       const void* dRes, void* dX, float* part, void* dG, void* dB, int N, int C, int accumulate,
-                      hipStream_t st);
+                      PdeDrop drop, void* dD, hipStream_t st);
 hipError_t pde_gelu_fwd(const void* X, void* Y, int64_t n, hipStream_t st);
 hipError_t pde_gelu_bwd(const void* dY, const void* X, void* dX, int64_t n, hipStream_t st);
 hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
                          int write_grad, hipStream_t st);
 hipError_t pde_embed_fwd(const int64_t* idx, const void* wte, const void* wpe, void* out, int N, int T, int C,
-                         hipStream_t st);
+                         PdeDrop drop, hipStream_t st);
 hipError_t pde_embed_bwd(const void* dX, const int64_t* idx, void* dwte, void* dwpe, float* acc, uint8_t* touched,
-                         int N, int T, int C, int Vp, int accumulate_pos, hipStream_t st);
+                         int N, int T, int C, int Vp, int accumulate_pos, PdeDrop drop, hipStream_t st);
 hipError_t pde_sumsq_bf16(const void* g, int64_t n, float scale, float* out, float* step_inc, hipStream_t st);
 hipError_t pde_adamw_master(float* master, void* p16, const void* g16, float* m, float* v, int64_t n, float lr,
                             float b1, float b2, float eps, float wd, float grad_scale, int step,
@@ -191,11 +208,12 @@ hipError_t pde_gemm_reduce(const float* part, int S, int M, int N, void* dw, con
 
 // ---- attention (attention.hip) ----
 void pde_attn_set_variant(int v);
+// drop.rng != nullptr: dropout on the attention probabilities (the DROP instantiations of the kernels)
 hipError_t pde_attn_fwd(const void* q, const void* k, const void* v, int ldq, void* o, int ldo, float* lse, int B,
-                        int T, int H, float scale, hipStream_t st);
+                        int T, int H, float scale, PdeDrop drop, hipStream_t st);
 hipError_t pde_attn_bwd(const void* q, const void* k, const void* v, int ldq, const void* o, const void* dout,
                         int ldo, const float* lse, float* Dd, void* dq, void* dk, void* dv, int B, int T, int H,
-                        float scale, hipStream_t st);
+                        float scale, PdeDrop drop, hipStream_t st);
 
 
 // ---- resnet (resnet.hip) ----

@@ -27,12 +27,21 @@
 // offsets (the builtin makes hipcc drain the DMA queue before each one).  exp2 is the bare
 // v_exp_f32 (inputs <= 0; no denormal fix-up), and the O rescale is skipped when no query's
 // running max grew (cdna_hip_programming.md T13 with threshold 0: exact).
+//
+// Dropout on the attention probabilities is the DROP template parameter of the three kernels; the
+// DROP = false instantiations are the code described above, unchanged.  The mask is a pure function
+// of (batch, head, query, key) (pde_rng.h: one Philox call covers a 4 x 4 block of queries x keys, a
+// byte each), regenerated in every kernel and never stored.  Forward: the running sum l and the stored
+// LSE use the undropped probabilities, only the P fragment fed to the V^T P^T MFMA is masked, and
+// 1 / keep is folded into the final 1 / l multiply.  Backward: dS = P o (M o dP / keep - D) with
+// D = rowsum(dO o O) as before (O is the dropped output), and dV takes the masked, scaled P.
 #include <type_traits>
 
 #include "pde_hip.h"
 #include "pde_bf16.h"
 #include "pde_kernels.h"
 #include "pde_lds.h"
+#include "pde_rng.h"
 
 namespace {
 
@@ -94,6 +103,62 @@ __device__ __forceinline__ void store_dimrows(bf16_t* dst, const f32x16& a0, con
   }
 }
 
+// lane s of every aligned group of 4 lanes, broadcast to the 4 (DPP quad_perm [s, s, s, s])
+template <int S>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, S * 0x55, 0xf, 0xf, false);
+}
+// word (j) of the 4 words lane S of the quad holds
+template <int S>
+__device__ __forceinline__ uint32_t quad_word(const uint32_t (&w)[4], int j) {
+  const uint32_t b0 = quad_bcast<S>(w[0]), b1 = quad_bcast<S>(w[1]), b2 = quad_bcast<S>(w[2]), b3 = quad_bcast<S>(w[3]);
+  return (j & 2) ? ((j & 1) ? b3 : b2) : ((j & 1) ? b1 : b0);
+}
+// byte (j) of each of the 4 words lane S of the quad holds, packed (byte e <- word e)
+template <int S>
+__device__ __forceinline__ uint32_t quad_bytes(const uint32_t (&w)[4], int j) {
+  const uint32_t sh = 8u * j;
+  return ((quad_bcast<S>(w[0]) >> sh) & 0xffu) | (((quad_bcast<S>(w[1]) >> sh) & 0xffu) << 8) |
+         (((quad_bcast<S>(w[2]) >> sh) & 0xffu) << 16) | (((quad_bcast<S>(w[3]) >> sh) & 0xffu) << 24);
+}
+
+// Dropout site of a launch, snapshot words loaded once (uniform address: scalar loads).
+// The 4 lanes of an aligned quad always need the SAME Philox groups (forward / dQ: 4 consecutive
+// queries, one word each; dK/dV: 4 consecutive keys, one byte of every word), so each lane draws a
+// quarter of the quad's groups and the words travel by DPP: 2 Philox calls per lane and 64-key tile
+// instead of 8.  Every call site is wave-uniform (all 64 lanes active), which the DPP reads rely on.
+struct AttnDrop {
+  uint32_t st[4];
+  uint32_t site, thr;
+  float inv_keep;
+  __device__ __forceinline__ explicit AttnDrop(const PdeDrop& d) : site(d.site), thr(d.thr), inv_keep(d.inv_keep) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) st[i] = d.rng[i];
+  }
+  // forward / dQ layout, one 64-key tile of query q (lane = q & 3 of its quad; the quad's queries are
+  // 4(q/4)..): w0[c] / w1[c] = the word of q over keys kbase + 8c .. +3 / kbase + 32 + 8c .. +3 (a byte per
+  // key; kbase = tile start + 4 * lane half).  Lane j draws the groups of c = j.
+  __device__ __forceinline__ void query_words(int bh, int T, int q, int kbase, uint32_t (&w0)[4],
+                                              uint32_t (&w1)[4]) const {
+    const int j = q & 3;
+    uint32_t a[4], b[4];
+    pde_rng::group_words(st, site, pde_rng::attn_group(bh, T, q, kbase + 8 * j), a);
+    pde_rng::group_words(st, site, pde_rng::attn_group(bh, T, q, kbase + 32 + 8 * j), b);
+    w0[0] = quad_word<0>(a, j); w0[1] = quad_word<1>(a, j); w0[2] = quad_word<2>(a, j); w0[3] = quad_word<3>(a, j);
+    w1[0] = quad_word<0>(b, j); w1[1] = quad_word<1>(b, j); w1[2] = quad_word<2>(b, j); w1[3] = quad_word<3>(b, j);
+  }
+  // dK/dV layout, 32 queries of key k (lane = k & 3 of its quad): kw[g] holds key k's bytes over the 4
+  // queries qbase + 8g .. +3 (byte e = query qbase + 8g + e; qbase = half start + 4 * lane half).
+  // Lane j draws the group of g = j.
+  __device__ __forceinline__ void key_words(int bh, int T, int qbase, int k, uint32_t (&kw)[4]) const {
+    const int j = k & 3;
+    uint32_t a[4];
+    pde_rng::group_words(st, site, pde_rng::attn_group(bh, T, qbase + 8 * j, k), a);
+    kw[0] = quad_bytes<0>(a, j); kw[1] = quad_bytes<1>(a, j); kw[2] = quad_bytes<2>(a, j); kw[3] = quad_bytes<3>(a, j);
+  }
+  __device__ __forceinline__ bool kept(uint32_t word, int e) const { return ((word >> (8 * e)) & 0xffu) >= thr; }
+};
+
 // ------------------------------------------------------------------------------------ block map
 // (tile, batch*head) of this block.  The dispatcher deals blocks to the 8 XCDs round-robin, so with a
 // plain 2-D grid the tiles of one (batch, head) land on every XCD and each XCD re-fetches that head's
@@ -114,11 +179,11 @@ __device__ __forceinline__ void attn_block(int nt, int nbh, int G, bool heavy_hi
 
 // ------------------------------------------------------------------------------------ forward
 // grid (T/128 * B*H), 256 threads: wave w owns queries qt*128 + 32w + (0..31)
-template <int NST, int OCC>
+template <int NST, int OCC, bool DROP>
 __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                      const bf16_t* __restrict__ V, int ldq, bf16_t* __restrict__ O,
                                                      int ldo, float* __restrict__ LSE, int T, int H, float sl2,
-                                                     float scale, int G) {
+                                                     float scale, int G, PdeDrop drop) {
   __shared__ __attribute__((aligned(16))) char lds[NST * 2 * TILE];  // stage: K | V
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h = lane >> 5, r = lane & 31;
   int qt, bh;
@@ -196,6 +261,19 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict_
         ls += s0[i] + s1[i];
       }
       l += ls;
+      if constexpr (DROP) {   // only the P fed to the MFMA is masked; l (and so the LSE) stays undropped
+        const AttnDrop ad(drop);
+        uint32_t w0[4], w1[4];
+        ad.query_words(bh, T, myq, k0 + 4 * h, w0, w1);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            s0[4 * c + e] = ad.kept(w0[c], e) ? s0[4 * c + e] : 0.f;
+            s1[4 * c + e] = ad.kept(w1[c], e) ? s1[4 * c + e] : 0.f;
+          }
+        }
+      }
       const bf16x8 p0 = frag_of<0>(s0), p1 = frag_of<1>(s0), p2 = frag_of<0>(s1), p3 = frag_of<1>(s1);
       lgkm_fence();
       o0 = mfma_bf16(v00, p0, o0);
@@ -209,7 +287,8 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict_
     }
   }
   const float lt = l + __shfl_xor(l, 32, 64);
-  store_dimrows(O + (size_t)b * T * ldo + (size_t)myq * ldo + hh * HD, o0, o1, 1.f / lt, h);
+  store_dimrows(O + (size_t)b * T * ldo + (size_t)myq * ldo + hh * HD, o0, o1,
+                DROP ? drop.inv_keep / lt : 1.f / lt, h);
   // log-sum-exp in base-2 units of the scaled scores (what the backward's exp2 consumes directly)
   if (h == 0) LSE[(size_t)bh * T + myq] = m * sl2 + __log2f(lt);
 }
@@ -220,13 +299,13 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict_
 // Dd[bh, t] = sum_d dO * O of its query rows is computed here, from the dO fragments it loads anyway
 // plus the O rows (each lane pair holds a row's 64 dims), and written for k_attn_bwd_dkdv, which runs
 // after it: no separate pre-pass over dO and O (14.6 us per layer at the GPT-2 shape).
-template <int NST, int OCC>
+template <int NST, int OCC, bool DROP>
 __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                         const bf16_t* __restrict__ V, int ldq,
                                                         const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO,
                                                         int ldo, const float* __restrict__ LSE,
                                                         float* __restrict__ Dd, bf16_t* __restrict__ dQ, int T, int H,
-                                                        float sl2, float scale, int G) {
+                                                        float sl2, float scale, int G, PdeDrop drop) {
   __shared__ __attribute__((aligned(16))) char lds[NST * 2 * TILE];  // stage: K | V
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h = lane >> 5, r = lane & 31;
   int qt, bh;
@@ -288,6 +367,19 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(const bf16_t* __restri
       const bf16x8 k00 = tfrag<0, 0>(kb), k01 = tfrag<0, 1>(kb), k10 = tfrag<1, 0>(kb), k11 = tfrag<1, 1>(kb);
       const bf16x8 k20 = tfrag<2, 0>(kb), k21 = tfrag<2, 1>(kb), k30 = tfrag<3, 0>(kb), k31 = tfrag<3, 1>(kb);
       const bool diag = k0 + 63 > q0;
+      if constexpr (DROP) {   // dP <- M o dP / keep
+        const AttnDrop ad(drop);
+        uint32_t w0[4], w1[4];
+        ad.query_words(bh, T, myq, k0 + 4 * h, w0, w1);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            d0[4 * c + e] = ad.kept(w0[c], e) ? d0[4 * c + e] * ad.inv_keep : 0.f;
+            d1[4 * c + e] = ad.kept(w1[c], e) ? d1[4 * c + e] * ad.inv_keep : 0.f;
+          }
+        }
+      }
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int key = k0 + (i & 3) + 8 * (i >> 2) + 4 * h;
@@ -318,14 +410,14 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(const bf16_t* __restri
 // dK, dV: grid (T/128 * B*H); wave w owns keys kb*128 + 32w + (0..31); loops over 64-query tiles
 // with Q / dO / LSE / D staged in LDS (rows for S / dP, transposed reads for dK / dV).
 constexpr int kDkdvStage = 2 * TILE + 512;           // Q | dO | LSE[64] | D[64]
-template <int NST, int OCC>
+template <int NST, int OCC, bool DROP>
 __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                           const bf16_t* __restrict__ V, int ldq,
                                                           const bf16_t* __restrict__ dO, int ldo,
                                                           const float* __restrict__ LSE,
                                                           const float* __restrict__ Dd, bf16_t* __restrict__ dK,
                                                           bf16_t* __restrict__ dV, int T, int H, float sl2,
-                                                          float scale, int G) {
+                                                          float scale, int G, PdeDrop drop) {
   __shared__ __attribute__((aligned(16))) char lds[NST * kDkdvStage];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h = lane >> 5, r = lane & 31;
   int kb, bh;
@@ -390,6 +482,8 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __rest
         // the causal mask only matters where this wave's keys reach past the half's first query
         // (wave-uniform): the other tiles skip the per-element compare / select
         const bool need_mask = k0 + 31 > qbase + 32 * u;
+        uint32_t kws[4] = {0u, 0u, 0u, 0u};
+        if constexpr (DROP) AttnDrop(drop).key_words(bh, T, qbase + 32 * u + 4 * h, myk, kws);
         auto softmax_grad = [&](auto MASK_) {
           constexpr bool MASK = decltype(MASK_)::value;
 #pragma unroll
@@ -398,6 +492,8 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __rest
             const float4 d4 = *reinterpret_cast<const float4*>(&Ds[32 * u + 8 * g + 4 * h]);
             const float lv[4] = {l4.x, l4.y, l4.z, l4.w};   // base-2 log-sum-exp (k_attn_fwd)
             const float dv[4] = {d4.x, d4.y, d4.z, d4.w};
+            const uint32_t kw = kws[g];
+            const float ik = drop.inv_keep;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int i = 4 * g + e;
@@ -406,8 +502,14 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __rest
                 const int q = qbase + 32 * u + 8 * g + 4 * h + e;
                 p = myk > q ? 0.f : p;
               }
-              S[i] = p;
-              dP[i] = p * (dP[i] - dv[e]);
+              if constexpr (DROP) {   // dV takes the masked, scaled P; dS = P o (M o dP / keep - D)
+                const bool keep = ((kw >> (8 * e)) & 0xffu) >= drop.thr;
+                S[i] = keep ? p * ik : 0.f;
+                dP[i] = p * ((keep ? dP[i] * ik : 0.f) - dv[e]);
+              } else {
+                S[i] = p;
+                dP[i] = p * (dP[i] - dv[e]);
+              }
             }
           }
         };
@@ -443,28 +545,30 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __rest
 int g_attn_variant = 5;   // pde_attn_set_variant: LDS ring depth / occupancy (default: measured best)
 int g_attn_group = kAttnGroup;   // heads per L2 group of the block map (0: plain order)
 
-template <int NST, int OCC>
+template <int NST, int OCC, bool DROP>
 void launch_fwd(const void* q, const void* k, const void* v, int ldq, void* o, int ldo, float* lse, int B, int T,
-                int H, float scale, hipStream_t st) {
-  hipLaunchKernelGGL((k_attn_fwd<NST, OCC>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
+                int H, float scale, PdeDrop drop, hipStream_t st) {
+  hipLaunchKernelGGL((k_attn_fwd<NST, OCC, DROP>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, ldq, (bf16_t*)o, ldo, lse, T, H, scale * 1.4426950408889634f,
-                     scale, g_attn_group);
+                     scale, g_attn_group, drop);
 }
 
-template <int NST, int OCC>
+template <int NST, int OCC, bool DROP>
 void launch_dq(const void* q, const void* k, const void* v, int ldq, const void* o, const void* dout, int ldo,
-               const float* lse, float* Dd, void* dq, int B, int T, int H, float sl2, float scale, hipStream_t st) {
-  hipLaunchKernelGGL((k_attn_bwd_dq<NST, OCC>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
+               const float* lse, float* Dd, void* dq, int B, int T, int H, float sl2, float scale, PdeDrop drop,
+               hipStream_t st) {
+  hipLaunchKernelGGL((k_attn_bwd_dq<NST, OCC, DROP>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, ldq, (const bf16_t*)o, (const bf16_t*)dout, ldo, lse, Dd,
-                     (bf16_t*)dq, T, H, sl2, scale, g_attn_group);
+                     (bf16_t*)dq, T, H, sl2, scale, g_attn_group, drop);
 }
 
-template <int NST, int OCC>
+template <int NST, int OCC, bool DROP>
 void launch_dkdv(const void* q, const void* k, const void* v, int ldq, const void* dout, int ldo, const float* lse,
-                 const float* Dd, void* dk, void* dv, int B, int T, int H, float sl2, float scale, hipStream_t st) {
-  hipLaunchKernelGGL((k_attn_bwd_dkdv<NST, OCC>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
+                 const float* Dd, void* dk, void* dv, int B, int T, int H, float sl2, float scale, PdeDrop drop,
+                 hipStream_t st) {
+  hipLaunchKernelGGL((k_attn_bwd_dkdv<NST, OCC, DROP>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, ldq, (const bf16_t*)dout, ldo, lse, Dd, (bf16_t*)dk,
-                     (bf16_t*)dv, T, H, sl2, scale, g_attn_group);
+                     (bf16_t*)dv, T, H, sl2, scale, g_attn_group, drop);
 }
 
 }  // namespace
@@ -482,23 +586,31 @@ void pde_attn_set_variant(int v) {
 }
 
 hipError_t pde_attn_fwd(const void* q, const void* k, const void* v, int ldq, void* o, int ldo, float* lse, int B,
-                        int T, int H, float scale, hipStream_t st) {
+                        int T, int H, float scale, PdeDrop drop, hipStream_t st) {
   if (T % 128 != 0) return hipErrorInvalidValue;
-  if (g_attn_variant & 1) launch_fwd<3, 3>(q, k, v, ldq, o, ldo, lse, B, T, H, scale, st);
-  else launch_fwd<kNstDefault, 2>(q, k, v, ldq, o, ldo, lse, B, T, H, scale, st);
+  if (drop.rng) {   // same ring depth / occupancy choice as the undropped forward (152 VGPRs: 3 blocks per CU fit)
+    if (g_attn_variant & 1) launch_fwd<3, 3, true>(q, k, v, ldq, o, ldo, lse, B, T, H, scale, drop, st);
+    else launch_fwd<kNstDefault, 2, true>(q, k, v, ldq, o, ldo, lse, B, T, H, scale, drop, st);
+  } else if (g_attn_variant & 1) launch_fwd<3, 3, false>(q, k, v, ldq, o, ldo, lse, B, T, H, scale, drop, st);
+  else launch_fwd<kNstDefault, 2, false>(q, k, v, ldq, o, ldo, lse, B, T, H, scale, drop, st);
   return hipGetLastError();
 }
 
 hipError_t pde_attn_bwd(const void* q, const void* k, const void* v, int ldq, const void* o, const void* dout,
                         int ldo, const float* lse, float* Dd, void* dq, void* dk, void* dv, int B, int T, int H,
-                        float scale, hipStream_t st) {
+                        float scale, PdeDrop drop, hipStream_t st) {
   if (T % 128 != 0) return hipErrorInvalidValue;
   const float sl2 = scale * 1.4426950408889634f;
   // dQ first: it computes and writes Dd (= rowsum dO * O), which the dK / dV kernel reads
-  if (g_attn_variant & 2) launch_dq<3, 3>(q, k, v, ldq, o, dout, ldo, lse, Dd, dq, B, T, H, sl2, scale, st);
-  else launch_dq<kNstDefault, 2>(q, k, v, ldq, o, dout, ldo, lse, Dd, dq, B, T, H, sl2, scale, st);
-  if (g_attn_variant & 4) launch_dkdv<3, 2>(q, k, v, ldq, dout, ldo, lse, Dd, dk, dv, B, T, H, sl2, scale, st);
-  else launch_dkdv<kNstDefault, 2>(q, k, v, ldq, dout, ldo, lse, Dd, dk, dv, B, T, H, sl2, scale, st);
+  if (drop.rng) {   // dQ at 2 blocks per CU (224 VGPRs), dK/dV with the default 3-deep ring (231 VGPRs)
+    launch_dq<kNstDefault, 2, true>(q, k, v, ldq, o, dout, ldo, lse, Dd, dq, B, T, H, sl2, scale, drop, st);
+    launch_dkdv<3, 2, true>(q, k, v, ldq, dout, ldo, lse, Dd, dk, dv, B, T, H, sl2, scale, drop, st);
+    return hipGetLastError();
+  }
+  if (g_attn_variant & 2) launch_dq<3, 3, false>(q, k, v, ldq, o, dout, ldo, lse, Dd, dq, B, T, H, sl2, scale, drop, st);
+  else launch_dq<kNstDefault, 2, false>(q, k, v, ldq, o, dout, ldo, lse, Dd, dq, B, T, H, sl2, scale, drop, st);
+  if (g_attn_variant & 4) launch_dkdv<3, 2, false>(q, k, v, ldq, dout, ldo, lse, Dd, dk, dv, B, T, H, sl2, scale, drop, st);
+  else launch_dkdv<kNstDefault, 2, false>(q, k, v, ldq, dout, ldo, lse, Dd, dk, dv, B, T, H, sl2, scale, drop, st);
   return hipGetLastError();
 }
 

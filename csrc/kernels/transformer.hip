@@ -10,11 +10,32 @@
 #include "pde_bf16.h"
 #include "pde_kernels.h"
 #include "pde_lr.h"
+#include "pde_rng.h"
 
 namespace {
 
+// Dropout at an elementwise site (pde_rng.h): keep flags of the 4 consecutive elements of `group`.
+struct DropSite {
+  uint32_t st[4];
+  uint32_t site, thr;
+  float inv_keep;
+  __device__ __forceinline__ explicit DropSite(const PdeDrop& d) : site(d.site), thr(d.thr), inv_keep(d.inv_keep) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) st[i] = d.rng[i];     // uniform address: scalar loads
+  }
+  // v[e] = kept ? v[e] / keep : 0
+  __device__ __forceinline__ void apply(uint64_t group, float (&v)[4]) const {
+    uint32_t w[4];
+    pde_rng::group_words(st, site, group, w);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = w[e] >= thr ? v[e] * inv_keep : 0.f;
+  }
+};
+
 // ---------------------------------------------------------------------------------- LayerNorm
-template <int NCH>
+template <int NCH, bool DROP>
+// With DROP, D is dropped first (site of `drop`; element index = its offset in the [N, C] tensor):
+// s = x + mask * d / keep, still one rounding to bf16, so s == x exactly where d was dropped.
 // With D != nullptr the row is first summed with D (the residual add of a pre-LN block), rounded to
 // bf16 exactly like a separate bf16 add would, written to S, and normalised: one pass instead of an
 // elementwise add kernel (read 2, write 1) followed by the LayerNorm (read 1).
@@ -22,7 +43,7 @@ __global__ __launch_bounds__(256) void k_ln_fwd(const bf16_t* __restrict__ X, co
                                                 bf16_t* __restrict__ S, const bf16_t* __restrict__ G,
                                                 const bf16_t* __restrict__ Bt, bf16_t* __restrict__ Y,
                                                 float* __restrict__ mean_out, float* __restrict__ rstd_out, int N,
-                                                int C, float eps) {
+                                                int C, float eps, PdeDrop drop) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;  // wave-uniform
@@ -48,6 +69,7 @@ __global__ __launch_bounds__(256) void k_ln_fwd(const bf16_t* __restrict__ X, co
       float a[4], b[4];
       unpack4(wx[j], a);
       unpack4(wd[j], b);
+      if constexpr (DROP) DropSite(drop).apply((uint64_t)row * nc + min(lane + 64 * j, nc - 1), b);
 #pragma unroll
       for (int e = 0; e < 4; ++e) a[e] += b[e];
       wx[j] = pack4(a);
@@ -93,12 +115,14 @@ __global__ __launch_bounds__(256) void k_ln_fwd(const bf16_t* __restrict__ X, co
 
 // dX = rstd * (gy - mean(gy) - xhat * mean(gy * xhat)) (+ dRes), gy = dY * gamma.
 // Block = 4 waves x RPW rows each; dgamma / dbeta partial sums per block -> part[blk][2][C].
-template <int NCH>
+// With DROP the same pass also writes dD = mask * dX / keep, the gradient of the dropped summand d of
+// k_ln_fwd's s = x + drop(d) (x itself receives dX).
+template <int NCH, bool DROP>
 __global__ __launch_bounds__(256) void k_ln_bwd(const bf16_t* __restrict__ dY, const bf16_t* __restrict__ X,
                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
                                                 const bf16_t* __restrict__ G, const bf16_t* __restrict__ dRes,
                                                 bf16_t* __restrict__ dX, float* __restrict__ part, int N, int C,
-                                                int rpw) {
+                                                int rpw, PdeDrop drop, bf16_t* __restrict__ dD) {
   extern __shared__ float sh[];  // [4][2][C]
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int nc = C >> 2;
@@ -164,6 +188,10 @@ __global__ __launch_bounds__(256) void k_ln_bwd(const bf16_t* __restrict__ dY, c
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = rs * (gy[j][e] - a - xh[j][e] * b) + r[e];
       if (c < nc) dxr[c] = pack4(o);
+      if constexpr (DROP) {
+        DropSite(drop).apply((uint64_t)row * nc + min(c, nc - 1), o);
+        if (c < nc) reinterpret_cast<uint2*>(dD + (size_t)row * C)[c] = pack4(o);
+      }
     }
     if (more) {
 #pragma unroll
@@ -533,9 +561,11 @@ __global__ __launch_bounds__(256) void k_xent_bf16(bf16_t* __restrict__ L, const
 }
 
 // ---------------------------------------------------------------------------------- embeddings
+// DROP: embedding dropout applied while writing (element index = offset in the [N, C] output)
+template <bool DROP>
 __global__ __launch_bounds__(256) void k_embed_fwd(const int64_t* __restrict__ idx, const bf16_t* __restrict__ wte,
                                                    const bf16_t* __restrict__ wpe, bf16_t* __restrict__ out, int N,
-                                                   int T, int C) {
+                                                   int T, int C, PdeDrop drop) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
@@ -550,13 +580,16 @@ __global__ __launch_bounds__(256) void k_embed_fwd(const int64_t* __restrict__ i
     unpack4(b[c], y);
 #pragma unroll
     for (int e = 0; e < 4; ++e) x[e] += y[e];
+    if constexpr (DROP) DropSite(drop).apply((uint64_t)row * (C >> 2) + c, x);
     o[c] = pack4(x);
   }
 }
 
 // dwpe[t, :] = sum_b dX[b*T + t, :]  (thread per (t, 4-column chunk); no atomics)
+// DROP (both backward kernels): the forward's mask and scale are applied to dX as it is read
+template <bool DROP>
 __global__ __launch_bounds__(256) void k_embed_bwd_pos(const bf16_t* __restrict__ dX, bf16_t* __restrict__ dwpe,
-                                                       int N, int T, int C, int accumulate) {
+                                                       int N, int T, int C, int accumulate, PdeDrop drop) {
   const int nc = C >> 2;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= T * nc) return;
@@ -565,6 +598,7 @@ __global__ __launch_bounds__(256) void k_embed_bwd_pos(const bf16_t* __restrict_
   for (int r = t; r < N; r += T) {
     float x[4];
     unpack4(reinterpret_cast<const uint2*>(dX + (size_t)r * C)[c], x);
+    if constexpr (DROP) DropSite(drop).apply((uint64_t)r * nc + c, x);
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[e] += x[e];
   }
@@ -579,9 +613,10 @@ __global__ __launch_bounds__(256) void k_embed_bwd_pos(const bf16_t* __restrict_
 }
 
 // token rows: fp32 atomics into a scratch table + a per-row touched flag
+template <bool DROP>
 __global__ __launch_bounds__(256) void k_embed_bwd_tok(const bf16_t* __restrict__ dX, const int64_t* __restrict__ idx,
                                                        float* __restrict__ acc, uint8_t* __restrict__ touched, int N,
-                                                       int C) {
+                                                       int C, PdeDrop drop) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
@@ -591,7 +626,19 @@ __global__ __launch_bounds__(256) void k_embed_bwd_tok(const bf16_t* __restrict_
   // one float per lane and instruction, lanes on consecutive addresses: every atomic wave-instruction
   // adds 256 contiguous bytes (full atomic rate; the 4-values-per-lane form hit 16-byte strides)
   const bf16_t* x = dX + (size_t)row * C;
-  for (int c = lane; c < C; c += 64) atomicAdd(a + c, bf2f(x[c]));
+  if constexpr (DROP) {
+    // every lane draws the group of its column (4 lanes share one) and takes its own word: the
+    // atomics keep their one-float-per-lane shape; dropped elements add nothing
+    const DropSite ds(drop);
+    for (int c = lane; c < C; c += 64) {
+      uint32_t w[4];
+      pde_rng::group_words(ds.st, ds.site, (uint64_t)row * (C >> 2) + (c >> 2), w);
+      const uint32_t mine = (c & 2) ? ((c & 1) ? w[3] : w[2]) : ((c & 1) ? w[1] : w[0]);
+      if (mine >= ds.thr) atomicAdd(a + c, bf2f(x[c]) * ds.inv_keep);
+    }
+  } else {
+    for (int c = lane; c < C; c += 64) atomicAdd(a + c, bf2f(x[c]));
+  }
 }
 
 // dwte[v] += acc[v] for touched rows; resets acc / touched for the next step (no memset needed)
@@ -851,14 +898,20 @@ inline int grid_for(int64_t n, int per_block, int cap = 4096) {
 extern "C" {
 
 hipError_t pde_ln_fwd(const void* X, const void* D, void* S, const void* G, const void* B, void* Y, float* mean,
-                      float* rstd, int N, int C, float eps, hipStream_t st) {
+                      float* rstd, int N, int C, float eps, PdeDrop drop, hipStream_t st) {
   const int nch = (C / 4 + 63) / 64;
   dim3 grid((N + 3) / 4);
+  if (drop.rng && !D) return hipErrorInvalidValue;   // dropout acts on the residual summand
 #define LNF(K)                                                                                          \
   case K:                                                                                               \
-    hipLaunchKernelGGL(k_ln_fwd<K>, grid, dim3(256), 0, st, (const bf16_t*)X, (const bf16_t*)D,          \
-                       (bf16_t*)S, (const bf16_t*)G,                                                    \
-                       (const bf16_t*)B, (bf16_t*)Y, mean, rstd, N, C, eps);                            \
+    if (drop.rng)                                                                                       \
+      hipLaunchKernelGGL((k_ln_fwd<K, true>), grid, dim3(256), 0, st, (const bf16_t*)X, (const bf16_t*)D, \
+                         (bf16_t*)S, (const bf16_t*)G,                                                  \
+                         (const bf16_t*)B, (bf16_t*)Y, mean, rstd, N, C, eps, drop);                    \
+    else                                                                                                \
+      hipLaunchKernelGGL((k_ln_fwd<K, false>), grid, dim3(256), 0, st, (const bf16_t*)X, (const bf16_t*)D, \
+                         (bf16_t*)S, (const bf16_t*)G,                                                  \
+                         (const bf16_t*)B, (bf16_t*)Y, mean, rstd, N, C, eps, drop);                    \
     break;
   switch (nch) {
     LNF(1) LNF(2) LNF(3) LNF(4) LNF(5) LNF(6) LNF(7) LNF(8)
@@ -879,15 +932,22 @@ int pde_ln_bwd_blocks(int N) {
 
 hipError_t pde_ln_bwd(const void* dY, const void* X, const float* mean, const float* rstd, const void* G,
                       const void* dRes, void* dX, float* part, void* dG, void* dB, int N, int C, int accumulate,
-                      hipStream_t st) {
+                      PdeDrop drop, void* dD, hipStream_t st) {
   const int nch = (C / 4 + 63) / 64;
   const int rpw = ln_bwd_rpw(N);
   const int nblk = (N + 4 * rpw - 1) / (4 * rpw);
   const size_t lds = (size_t)8 * C * sizeof(float);
+  if ((drop.rng != nullptr) != (dD != nullptr)) return hipErrorInvalidValue;
 #define LNB(K)                                                                                          \
   case K:                                                                                               \
-    hipLaunchKernelGGL(k_ln_bwd<K>, dim3(nblk), dim3(256), lds, st, (const bf16_t*)dY, (const bf16_t*)X, \
-                       mean, rstd, (const bf16_t*)G, (const bf16_t*)dRes, (bf16_t*)dX, part, N, C, rpw); \
+    if (drop.rng)                                                                                       \
+      hipLaunchKernelGGL((k_ln_bwd<K, true>), dim3(nblk), dim3(256), lds, st, (const bf16_t*)dY,        \
+                         (const bf16_t*)X, mean, rstd, (const bf16_t*)G, (const bf16_t*)dRes,           \
+                         (bf16_t*)dX, part, N, C, rpw, drop, (bf16_t*)dD);                              \
+    else                                                                                                \
+      hipLaunchKernelGGL((k_ln_bwd<K, false>), dim3(nblk), dim3(256), lds, st, (const bf16_t*)dY,       \
+                         (const bf16_t*)X, mean, rstd, (const bf16_t*)G, (const bf16_t*)dRes,           \
+                         (bf16_t*)dX, part, N, C, rpw, drop, (bf16_t*)dD);                              \
     break;
   switch (nch) {
     LNB(1) LNB(2) LNB(3) LNB(4) LNB(5) LNB(6) LNB(7) LNB(8)
@@ -935,18 +995,29 @@ hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V,
 }
 
 hipError_t pde_embed_fwd(const int64_t* idx, const void* wte, const void* wpe, void* out, int N, int T, int C,
-                         hipStream_t st) {
-  hipLaunchKernelGGL(k_embed_fwd, dim3((N + 3) / 4), dim3(256), 0, st, idx, (const bf16_t*)wte, (const bf16_t*)wpe,
-                     (bf16_t*)out, N, T, C);
+                         PdeDrop drop, hipStream_t st) {
+  if (drop.rng)
+    hipLaunchKernelGGL(k_embed_fwd<true>, dim3((N + 3) / 4), dim3(256), 0, st, idx, (const bf16_t*)wte,
+                       (const bf16_t*)wpe, (bf16_t*)out, N, T, C, drop);
+  else
+    hipLaunchKernelGGL(k_embed_fwd<false>, dim3((N + 3) / 4), dim3(256), 0, st, idx, (const bf16_t*)wte,
+                       (const bf16_t*)wpe, (bf16_t*)out, N, T, C, drop);
   return hipGetLastError();
 }
 
 hipError_t pde_embed_bwd(const void* dX, const int64_t* idx, void* dwte, void* dwpe, float* acc, uint8_t* touched,
-                         int N, int T, int C, int Vp, int accumulate_pos, hipStream_t st) {
-  hipLaunchKernelGGL(k_embed_bwd_pos, dim3((T * (C / 4) + 255) / 256), dim3(256), 0, st, (const bf16_t*)dX,
-                     (bf16_t*)dwpe, N, T, C, accumulate_pos);
-  hipLaunchKernelGGL(k_embed_bwd_tok, dim3((N + 3) / 4), dim3(256), 0, st, (const bf16_t*)dX, idx, acc, touched, N,
-                     C);
+                         int N, int T, int C, int Vp, int accumulate_pos, PdeDrop drop, hipStream_t st) {
+  if (drop.rng) {
+    hipLaunchKernelGGL(k_embed_bwd_pos<true>, dim3((T * (C / 4) + 255) / 256), dim3(256), 0, st, (const bf16_t*)dX,
+                       (bf16_t*)dwpe, N, T, C, accumulate_pos, drop);
+    hipLaunchKernelGGL(k_embed_bwd_tok<true>, dim3((N + 3) / 4), dim3(256), 0, st, (const bf16_t*)dX, idx, acc,
+                       touched, N, C, drop);
+  } else {
+    hipLaunchKernelGGL(k_embed_bwd_pos<false>, dim3((T * (C / 4) + 255) / 256), dim3(256), 0, st, (const bf16_t*)dX,
+                       (bf16_t*)dwpe, N, T, C, accumulate_pos, drop);
+    hipLaunchKernelGGL(k_embed_bwd_tok<false>, dim3((N + 3) / 4), dim3(256), 0, st, (const bf16_t*)dX, idx, acc,
+                       touched, N, C, drop);
+  }
   hipLaunchKernelGGL(k_embed_tok_merge, dim3((Vp + 3) / 4), dim3(256), 0, st, acc, touched, (bf16_t*)dwte, Vp, C);
   return hipGetLastError();
 }

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 from .._ext import kernels
 from ..parallel.flat import flat_grad_slot
 from . import gemm as G
+from . import rng as R
 
 _BF16 = torch.bfloat16
 
@@ -149,6 +150,78 @@ def add_layer_norm_residual(x, d, weight, bias, eps: float = 1e-5):
     return s, F.layer_norm(s, (s.shape[-1],), weight, bias, eps)
 
 
+# --------------------------------------------------------------------------------------- dropout
+def _drop_args(p, rng_snapshot, kind):
+    """(integer threshold, 1 / keep) of a dropping call at a site of ``kind`` (ops/rng.py)."""
+    if rng_snapshot is None:
+        raise ValueError("dropout with p > 0 needs an rng_snapshot (DeviceRNG.next())")
+    return R.threshold(p, kind), R.inv_keep(p, kind)
+
+
+def _cpu_drop(t, p, rng_snapshot, site):
+    """CPU definition of an elementwise site: t * mask / keep with the mask of ops/rng.py."""
+    m = R.elementwise_mask(rng_snapshot, site, t.numel(), p).view(t.shape)
+    return t * (m.to(t.dtype) * R.inv_keep(p, "elementwise"))
+
+
+class AddDropLayerNormResFn(torch.autograd.Function):
+    """(s, LayerNorm(s)) with s = x + dropout(d): mask and scale are applied inside the fused add +
+    LayerNorm kernel.  Backward is the one LayerNorm backward kernel, which also writes
+    dD = mask * dX / keep in the same pass (x receives dX)."""
+
+    @staticmethod
+    def forward(ctx, x, d, w, b, eps, snap, site, thr, ik):
+        xc, dc = _c(x), _c(d)
+        C = xc.shape[-1]
+        N = xc.numel() // C
+        s = torch.empty_like(xc)
+        y = torch.empty_like(xc)
+        mean = torch.empty(N, device=x.device, dtype=torch.float32)
+        rstd = torch.empty(N, device=x.device, dtype=torch.float32)
+        kernels().ln_fwd(xc, w, b, y, mean, rstd, eps, dc, s, snap, site, thr, ik)
+        ctx.save_for_backward(s, w, b, mean, rstd, snap)
+        ctx.drop = (site, thr, ik)
+        ctx.set_materialize_grads(False)
+        return s, y
+
+    @staticmethod
+    def backward(ctx, dres, dy):
+        x, w, b, mean, rstd, snap = ctx.saved_tensors
+        site, thr, ik = ctx.drop
+        C = x.shape[-1]
+        N = x.numel() // C
+        K = kernels()
+        dx = torch.empty_like(x)
+        dd = torch.empty_like(x)
+        part = torch.empty(K.ln_bwd_blocks(N) * 2 * C, device=x.device, dtype=torch.float32)
+        dw = flat_grad_slot(w)
+        dw = torch.empty(C, device=x.device, dtype=w.dtype) if dw is None else dw
+        db = flat_grad_slot(b)
+        db = torch.empty(C, device=x.device, dtype=w.dtype) if db is None else db
+        if dy is None:
+            dy = torch.zeros_like(x)
+        K.ln_bwd(_c(dy), x, mean, rstd, w, None if dres is None else _c(dres), dx, part, dw, db, False,
+                 dd, snap, site, thr, ik)
+        return dx, dd, dw, db, None, None, None, None, None
+
+
+def add_dropout_layer_norm_residual(x, d, weight, bias, eps: float = 1e-5, p: float = 0.0, rng_snapshot=None,
+                                    site: int = 0):
+    """Returns ``(s, layer_norm(s))`` with ``s = x + dropout(d, p)`` (residual dropout): the mask of
+    ``(rng_snapshot, site)`` and the ``1 / keep`` scale run inside the fused add + LayerNorm kernel,
+    forward and backward.  ``p == 0`` is ``add_layer_norm_residual``."""
+    if p == 0.0:
+        return add_layer_norm_residual(x, d, weight, bias, eps)
+    thr, ik = _drop_args(p, rng_snapshot, "elementwise")
+    if _gpu(x):
+        if x.shape != d.shape or x.dtype != d.dtype:
+            raise NotImplementedError(f"add_dropout_layer_norm_residual on GPU needs x and d of one shape and dtype "
+                                      f"(got {tuple(x.shape)} {x.dtype} and {tuple(d.shape)} {d.dtype})")
+        return AddDropLayerNormResFn.apply(x, d, weight, bias, eps, rng_snapshot, int(site), thr, ik)
+    s = x + _cpu_drop(d, p, rng_snapshot, site)
+    return s, F.layer_norm(s, (s.shape[-1],), weight, bias, eps)
+
+
 # --------------------------------------------------------------------------------------- GELU
 class GeluFn(torch.autograd.Function):
     @staticmethod
@@ -179,7 +252,7 @@ class CausalAttentionFn(torch.autograd.Function):
     """qkv: [B, T, 3*H*64] (the c_attn output, read in place) -> y: [B, T, H*64]."""
 
     @staticmethod
-    def forward(ctx, qkv, n_head):
+    def forward(ctx, qkv, n_head, snap=None, site=0, thr=0, ik=1.0):
         qkv = _c(qkv)
         B, T, C3 = qkv.shape
         C = C3 // 3
@@ -187,14 +260,18 @@ class CausalAttentionFn(torch.autograd.Function):
         o = torch.empty(B, T, C, device=qkv.device, dtype=qkv.dtype)
         lse = torch.empty(B * n_head * T, device=qkv.device, dtype=torch.float32)
         scale = 1.0 / math.sqrt(C // n_head)
-        kernels().attn_fwd(q, k, v, o, lse, n_head, scale)
-        ctx.save_for_backward(qkv, o, lse)
-        ctx.n_head, ctx.scale = n_head, scale
+        if snap is None:
+            kernels().attn_fwd(q, k, v, o, lse, n_head, scale)
+            ctx.save_for_backward(qkv, o, lse)
+        else:       # dropout on the probabilities, inside the flash kernels (the mask is never stored)
+            kernels().attn_fwd(q, k, v, o, lse, n_head, scale, snap, site, thr, ik)
+            ctx.save_for_backward(qkv, o, lse, snap)
+        ctx.n_head, ctx.scale, ctx.drop = n_head, scale, (site, thr, ik)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse = ctx.saved_tensors
+        qkv, o, lse, *snap = ctx.saved_tensors
         B, T, C3 = qkv.shape
         C = C3 // 3
         do = _c(do)
@@ -203,21 +280,38 @@ class CausalAttentionFn(torch.autograd.Function):
         sl = [slice(0, C), slice(C, 2 * C), slice(2 * C, 3 * C)]
         q, k, v = (qkv[:, :, s] for s in sl)
         dq, dk, dv = (dqkv[:, :, s] for s in sl)
-        kernels().attn_bwd(q, k, v, o, do, lse, Dd, dq, dk, dv, ctx.n_head, ctx.scale)
-        return dqkv, None
+        if snap:
+            kernels().attn_bwd(q, k, v, o, do, lse, Dd, dq, dk, dv, ctx.n_head, ctx.scale, snap[0], *ctx.drop)
+        else:
+            kernels().attn_bwd(q, k, v, o, do, lse, Dd, dq, dk, dv, ctx.n_head, ctx.scale)
+        return dqkv, None, None, None, None, None
 
 
-def causal_attention(qkv, n_head: int):
+def causal_attention(qkv, n_head: int, p: float = 0.0, rng_snapshot=None, site: int = 0):
+    """Causal self-attention over the fused c_attn output.  ``p > 0`` drops attention probabilities
+    (after the softmax) with the mask of ``(rng_snapshot, site)``; the probability realised is
+    ``rng.effective_p(p, "attention")`` and the kept ones are scaled by its ``1 / keep``.  ``p == 0``
+    takes the path without dropout."""
     if _gpu(qkv):
         C = qkv.shape[-1] // 3
         if C // n_head != 64:
             raise NotImplementedError("flash attention kernel: head_dim 64")
-        return CausalAttentionFn.apply(qkv, n_head)
+        if p == 0.0:
+            return CausalAttentionFn.apply(qkv, n_head)
+        thr, ik = _drop_args(p, rng_snapshot, "attention")
+        return CausalAttentionFn.apply(qkv, n_head, rng_snapshot, int(site), thr, ik)
     B, T, C3 = qkv.shape
     C = C3 // 3
     q, k, v = qkv.split(C, dim=2)
     q, k, v = (t.view(B, T, n_head, C // n_head).transpose(1, 2) for t in (q, k, v))
-    y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+    if p == 0.0:
+        y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+    else:
+        _drop_args(p, rng_snapshot, "attention")
+        s = (q @ k.transpose(-1, -2)) / math.sqrt(C // n_head)
+        s = s.masked_fill(torch.triu(torch.ones(T, T, dtype=torch.bool, device=qkv.device), 1), float("-inf"))
+        m = R.attention_mask(rng_snapshot, site, B, n_head, T, p)
+        y = (torch.softmax(s, -1) * (m.to(s.dtype) * R.inv_keep(p, "attention"))) @ v
     return y.transpose(1, 2).reshape(B, T, C)
 
 
@@ -241,13 +335,18 @@ class EmbeddingFn(torch.autograd.Function):
     paths (the LM head's backward runs first and leaves its dw in the pairing slot)."""
 
     @staticmethod
-    def forward(ctx, idx, wte, wpe):
+    def forward(ctx, idx, wte, wpe, snap=None, site=0, thr=0, ik=1.0):
         B, T = idx.shape
         C = wte.shape[1]
         idx = _c(idx.long())
         out = torch.empty(B, T, C, device=wte.device, dtype=wte.dtype)
-        kernels().embed_fwd(idx, wte, wpe, out, T)
-        ctx.save_for_backward(idx)
+        if snap is None:
+            kernels().embed_fwd(idx, wte, wpe, out, T)
+            ctx.save_for_backward(idx)
+        else:       # embedding dropout: mask and scale applied while writing
+            kernels().embed_fwd(idx, wte, wpe, out, T, snap, site, thr, ik)
+            ctx.save_for_backward(idx, snap)
+        ctx.drop = (site, thr, ik)
         ctx.shapes = (wte.shape, wpe.shape, T)
         ctx.tied = {}                  # filled by the LM head's backward of this forward pass, if tied
         ctx.wpe = wpe
@@ -256,7 +355,7 @@ class EmbeddingFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dx):
-        (idx,) = ctx.saved_tensors
+        idx, *snap = ctx.saved_tensors
         wte_shape, wpe_shape, T = ctx.shapes
         dw_tied = ctx.tied.pop("dw", None)
         if dw_tied is not None and tuple(dw_tied.shape) == tuple(wte_shape):
@@ -270,15 +369,24 @@ class EmbeddingFn(torch.autograd.Function):
         if T < wpe_shape[0]:
             dwpe[T:].zero_()                       # rows past the sequence get no gradient
         acc, touched = _emb_scratch(dx.device, wte_shape[0], wte_shape[1])
-        kernels().embed_bwd(_c(dx), idx, dwte, dwpe, acc, touched, T, False)
-        return None, ret_wte, dwpe
+        if snap:    # the forward's mask and scale are applied while dX is read
+            kernels().embed_bwd(_c(dx), idx, dwte, dwpe, acc, touched, T, False, snap[0], *ctx.drop)
+        else:
+            kernels().embed_bwd(_c(dx), idx, dwte, dwpe, acc, touched, T, False)
+        return None, ret_wte, dwpe, None, None, None, None
 
 
-def embedding(idx, wte, wpe):
+def embedding(idx, wte, wpe, p: float = 0.0, rng_snapshot=None, site: int = 0):
+    """Token + position embedding; ``p > 0`` applies embedding dropout with the mask of
+    ``(rng_snapshot, site)`` inside the kernels (forward while writing, backward while reading dX)."""
     if _gpu(wte):
-        return EmbeddingFn.apply(idx, wte, wpe)
+        if p == 0.0:
+            return EmbeddingFn.apply(idx, wte, wpe)
+        thr, ik = _drop_args(p, rng_snapshot, "elementwise")
+        return EmbeddingFn.apply(idx, wte, wpe, rng_snapshot, int(site), thr, ik)
     T = idx.shape[1]
-    return F.embedding(idx, wte) + wpe[:T].unsqueeze(0)
+    out = F.embedding(idx, wte) + wpe[:T].unsqueeze(0)
+    return out if p == 0.0 else _cpu_drop(out, p, rng_snapshot, site)
 
 
 # --------------------------------------------------------------------------------------- LM head + CE
