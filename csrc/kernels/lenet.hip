@@ -236,10 +236,19 @@ __global__ __launch_bounds__(256) void k_conv_fwd(const float* __restrict__ X, B
 // =================================================================================================
 // F2: H1 = relu(P2 @ W1^T + b1).  grid (32 n-tiles, ceil(B/16) m-tiles), block 256 (4 waves split K).
 // Lane-contiguous K: each lane loads 4 consecutive k of its A row and of its B column (W1 row) as
-// one float4; MFMA j uses element j.  The 13 K-chunks of a wave are fully unrolled so all 26
-// 16-B loads are in flight before the first MFMA.  Block (0,0) also advances the engine's device
-// counters (optimizer step, batch position): F1 of this step has already consumed them and the
-// fused Adam that follows reads the new optimizer step.
+// one float4; MFMA j uses element j.  The 13 K-chunks of a wave are fully unrolled; a scheduling
+// barrier holds the MFMA chain below the load batch, so the bias load and all 26 16-B loads are in
+// flight before the first MFMA, and the chain consumes them in issue order behind counted vmcnt
+// waits (tools/isa_load_order.py prints the compiled order: 27L w23 4M w22 4M ...).  Two things
+// used to defeat this.  Left alone, the compiler re-rolls the batch into 4 loads / vmcnt(0) /
+// 8 MFMAs (39 VGPRs, seven dependent round trips).  And a mask multiply on every operand let the
+// scheduler hoist the multiplies of late chunks into the MFMA shadow of early ones, where each
+// waits for its own (late) load: the chain then drained the whole batch before its third MFMA.
+// So operands go to the MFMAs unmasked (see below), and the one masked chunk sits behind a second
+// scheduling barrier.  112 VGPRs, which costs nothing at one block per CU.  Nothing is loaded
+// after the LDS barrier and the epilogue is one store per thread.  Block (0,0) also advances the
+// engine's device counters (optimizer step, batch position): F1 of this step has already consumed
+// them and the fused Adam that follows reads the new optimizer step.
 // =================================================================================================
 template <bool PROF>
 __global__ __launch_bounds__(256) void k_fc1_fwd(const float* __restrict__ P2, int B, const float* __restrict__ W,
@@ -252,9 +261,12 @@ __global__ __launch_bounds__(256) void k_fc1_fwd(const float* __restrict__ P2, i
   if (ctr && nt == 0 && mt == 0 && t == 0)
     for (int c = 0; c < nctr; ++c) ctr[c] += 1;
   const int row = mt * 16 + (l & 15), n = nt * 16 + (l & 15), kg = l >> 4;
-  const float am = row < B ? 1.f : 0.f, bm = n < kHid ? 1.f : 0.f;
+  // Rows >= B and columns >= kHid of the tile are computed from clamped (real) data and never
+  // stored: a matmul row / column depends on its own operand row / column only, so no mask is
+  // needed there.  Only the 13th K-chunk, which exists for waves 0 and 1 alone, is masked.
   const float4* ap = reinterpret_cast<const float4*>(P2 + (size_t)min(row, B - 1) * kFeat + kg * 4);
   const float4* bp = reinterpret_cast<const float4*>(W + (size_t)min(n, kHid - 1) * kFeat + kg * 4);
+  const float bvv = bias[min(n, kHid - 1)];
   float4 a[13], bb[13];
 #pragma unroll
   for (int i = 0; i < 13; ++i) {
@@ -262,29 +274,34 @@ __global__ __launch_bounds__(256) void k_fc1_fwd(const float* __restrict__ P2, i
     a[i] = ap[c * 4];
     bb[i] = bp[c * 4];
   }
-  const float bvv = bias[min(n, kHid - 1)];
+  __builtin_amdgcn_sched_barrier(0);           // every load above is issued before the first MFMA
   f32x4 acc0 = {0.f}, acc1 = {0.f};
 #pragma unroll
-  for (int i = 0; i < 13; ++i) {
-    const float km = (w + 4 * i < kFeat / 16) ? am : 0.f;
-    acc0 = mfma16x16x4(a[i].x * km, bb[i].x * bm, acc0);
-    acc1 = mfma16x16x4(a[i].y * km, bb[i].y * bm, acc1);
-    acc0 = mfma16x16x4(a[i].z * km, bb[i].z * bm, acc0);
-    acc1 = mfma16x16x4(a[i].w * km, bb[i].w * bm, acc1);
+  for (int i = 0; i < 12; ++i) {
+    acc0 = mfma16x16x4(a[i].x, bb[i].x, acc0);
+    acc1 = mfma16x16x4(a[i].y, bb[i].y, acc1);
+    acc0 = mfma16x16x4(a[i].z, bb[i].z, acc0);
+    acc1 = mfma16x16x4(a[i].w, bb[i].w, acc1);
   }
+  __builtin_amdgcn_sched_barrier(0);           // the mask multiplies below stay here: hoisted into the MFMA
+  {                                            // shadow above they would wait for the last load first
+    const float km = (w + 48 < kFeat / 16) ? 1.f : 0.f;
+    acc0 = mfma16x16x4(a[12].x * km, bb[12].x, acc0);
+    acc1 = mfma16x16x4(a[12].y * km, bb[12].y, acc1);
+    acc0 = mfma16x16x4(a[12].z * km, bb[12].z, acc0);
+    acc1 = mfma16x16x4(a[12].w * km, bb[12].w, acc1);
+  }
+  asm volatile("" ::"v"(bvv));                 // a use above the barrier: the bias load is not sunk below it
+  // C layout: lane (l&15) owns column n, rows (l>>4)*4 + r
 #pragma unroll
   for (int r = 0; r < 4; ++r) red[w][(l >> 4) * 4 + r][l & 15] = acc0[r] + acc1[r];
   __syncthreads();
-  if (w == 0) {
-    // C layout: lane (l&15) owns column n, rows (l>>4)*4 + r
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = (l >> 4) * 4 + r, j = l & 15, gm = mt * 16 + i;
-      if (gm < B && n < kHid) {
-        const float v = red[0][i][j] + red[1][i][j] + red[2][i][j] + red[3][i][j] + bvv;
-        H1[(size_t)gm * kHid + n] = fmaxf(v, 0.f);
-      }
-    }
+  {
+    // thread t folds element (row t>>4, column t&15 == l&15: its own n and bias) in wave order:
+    // one store per thread, none waiting for another's acknowledgement
+    const int i = t >> 4, j = t & 15, gm = mt * 16 + i;
+    const float v = red[0][i][j] + red[1][i][j] + red[2][i][j] + red[3][i][j] + bvv;
+    if (gm < B && n < kHid) H1[(size_t)gm * kHid + n] = fmaxf(v, 0.f);
   }
   PMARK(1);
 }
@@ -464,7 +481,12 @@ __device__ __forceinline__ float block_sum256(float v, float* scratch) {
 }
 
 // =================================================================================================
-// B1: fc backward, three block roles in one launch (all loads of a wave issued before its MFMAs).
+// B1: fc backward, three block roles in one launch.  Roles A and B issue the loads of a K slice
+// before its MFMAs; role C is compiled as 9 loads up front and the other 31 between its MFMAs, with
+// the P2 mask load after the LDS barrier (tools/isa_load_order.py).  Issuing role C's 41 loads as
+// one batch needs 81 VGPRs (5 waves per SIMD, 1280 resident blocks for a grid of 2064); that, and
+// role A on 16x32 or 64x32 tiles to fit the grid, were measured slower
+// (profiles/lenet_load_order/rejected_fc_bwd_*).
 //   role C [0, nC)       : dP2m = (dZ1 @ W1) * (P2 > 0)      16x16 tiles, split-K over 4 waves
 //   role A [nC, nC+416)  : [dW1 | db1] = dZ1^T @ [P2 | 1]      16x16 tile per wave, K = B; n-tile 50
 //                          is the bias tile (B operand = ones column), so db1 costs one MFMA chain

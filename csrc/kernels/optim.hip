@@ -49,9 +49,12 @@ struct Fold {      // up to two replicated gradient ranges (LeNet: conv1 atomic 
 
 // Folded ranges (whole replica sets [off, off + nrep*stride)) are holes of the main index space;
 // appended fold blocks own them.  Each canonical float4 gets kLS lanes: lane l sums replicas
-// l, l+kLS, ... (all loads in flight at once), a 2-step xor shuffle combines the lanes, and lane l
-// then updates element l of the float4 (the old one-thread-per-float4 fold issued 19 loads per
-// thread on the last ~27 blocks and ended the kernel 2 us after every other block).
+// l, l+kLS, ..., a 2-step xor shuffle combines the lanes, and lane l then updates element l of the
+// float4 (the old one-thread-per-float4 fold issued 19 loads per thread on the last ~27 blocks and
+// ended the kernel 2 us after every other block).  The guarded loads compile to one basic block
+// each, with a vmcnt(0) between most of them (tools/isa_load_order.py); making them unconditional
+// on clamped addresses puts them in one batch but did not shorten the fold blocks
+// (profiles/lenet_load_order/rejected_adam_fold_batch/).
 constexpr int kMaxFold = 16;
 constexpr int kLS = 4;
 
@@ -235,7 +238,7 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, float* __re
     if (ar.nvb > 0) wait_epoch(ar.epoch, t, ar.pd);   // the reduced replicas must be complete
     const long long e0 = fold_elem(fd, fb);
     float pa = 0.f, ma = 0.f, va = 0.f;
-    if (e0 >= 0) {                                   // issued before the replica loads: one round trip
+    if (e0 >= 0) {                                   // issued before the replica loads
       pa = p[e0];
       ma = m[e0];
       va = v[e0];
