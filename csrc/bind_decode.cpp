@@ -1,0 +1,159 @@
+// torch bindings of the GPT-2 decode kernels (csrc/kernels/decode.hip).
+// Every entry validates device / dtype / contiguity / shape / alignment before launching on the current stream.
+#include "pde_bind.h"
+#include "pde_decode.h"
+
+namespace pde {
+namespace {
+
+void check_al16(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+}
+
+void check_state(const at::Tensor& state) {
+  check_cuda(state, "decode state", I32, PDE_DS_WORDS);
+  TORCH_CHECK(state.numel() == PDE_DS_WORDS, "decode state holds ", PDE_DS_WORDS, " words");
+}
+
+int64_t skinny_splits(int64_t N, int64_t K) { return pde_skinny_splits((int)N, (int)K); }
+
+void skinny_linear(const at::Tensor& x, const at::Tensor& w, const OptT& bias, const at::Tensor& y, const OptT& part,
+                   bool gelu) {
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && y.dim() == 2, "skinny_linear: x [M, K], w [N, K], y [M, N]");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(M >= 1 && M <= 16, "skinny_linear: 1 <= M <= 16, got ", M);
+  TORCH_CHECK(K % 64 == 0 && K >= 64 && N % 8 == 0 && N >= 8, "skinny_linear: K % 64 == 0 and N % 8 == 0, got K ", K,
+              ", N ", N);
+  TORCH_CHECK(w.size(1) == K && y.size(0) == M && y.size(1) == N, "skinny_linear: shapes do not match");
+  check_cuda(x, "x", BF16);
+  check_cuda(w, "w", BF16);
+  check_cuda(y, "y", BF16);
+  check_al16(x, "x");
+  check_al16(w, "w");
+  check_al16(y, "y");
+  const void* bp = optr<void>(bias, "bias", BF16, N);
+  TORCH_CHECK(bp == nullptr || reinterpret_cast<uintptr_t>(bp) % 8 == 0, "bias must be 8-byte aligned");
+  const int64_t S = pde_skinny_splits((int)N, (int)K);
+  float* pp = optr<float>(part, "part", F32, S > 1 ? S * M * N : 0);
+  TORCH_CHECK(S == 1 || pp != nullptr, "skinny_linear: this shape splits K ", S, " ways and needs `part`");
+  TORCH_CHECK(pp == nullptr || reinterpret_cast<uintptr_t>(pp) % 16 == 0, "part must be 16-byte aligned");
+  hip_check(pde_skinny_linear(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), pp, (int)M, (int)N, (int)K, gelu ? 1 : 0,
+                              cur_stream()),
+            "skinny_linear");
+}
+
+int64_t decode_attn_chunk() { return pde_decode_attn_chunk(); }
+
+// cache: one layer [2, B, H, Tmax, 64]
+void check_cache(const at::Tensor& cache, int64_t B, int64_t H) {
+  check_cuda(cache, "cache", BF16);
+  TORCH_CHECK(cache.dim() == 5 && cache.size(0) == 2 && cache.size(1) == B && cache.size(2) == H && cache.size(4) == 64,
+              "cache layer must be [2, B, H, Tmax, 64]");
+  check_al16(cache, "cache");
+}
+
+void decode_attention(const at::Tensor& qkv, const at::Tensor& cache, const at::Tensor& state, const at::Tensor& part,
+                      const at::Tensor& out, int64_t H, double scale) {
+  TORCH_CHECK(qkv.dim() == 2 && H >= 1 && qkv.size(1) == 3 * H * 64, "decode_attention: qkv must be [B, 3 * H * 64]");
+  const int64_t B = qkv.size(0);
+  check_cuda(qkv, "qkv", BF16);
+  check_al16(qkv, "qkv");
+  check_cache(cache, B, H);
+  const int64_t Tmax = cache.size(3), nch = (Tmax + pde_decode_attn_chunk() - 1) / pde_decode_attn_chunk();
+  check_state(state);
+  check_cuda(part, "part", F32, B * H * nch * 66);
+  check_cuda(out, "out", BF16, B * H * 64);
+  hip_check(pde_decode_attention(qkv.data_ptr(), cache.data_ptr(), ptr<int>(state), ptr<float>(part), out.data_ptr(),
+                                 (int)B, (int)H, (int)Tmax, (float)scale, cur_stream()),
+            "decode_attention");
+}
+
+void cache_fill(const at::Tensor& qkv, const at::Tensor& cache, int64_t T0, int64_t H) {
+  TORCH_CHECK(qkv.dim() == 3 && H >= 1 && qkv.size(2) == 3 * H * 64, "cache_fill: qkv must be [B, Tpad, 3 * H * 64]");
+  const int64_t B = qkv.size(0), Tpad = qkv.size(1);
+  check_cuda(qkv, "qkv", BF16);
+  check_al16(qkv, "qkv");
+  check_cache(cache, B, H);
+  TORCH_CHECK(T0 >= 1 && T0 <= Tpad && T0 <= cache.size(3), "cache_fill: 1 <= T0 <= min(Tpad, Tmax), got ", T0);
+  hip_check(pde_cache_fill(qkv.data_ptr(), cache.data_ptr(), (int)B, (int)H, (int)Tpad, (int)T0, (int)cache.size(3),
+                           cur_stream()),
+            "cache_fill");
+}
+
+void decode_embed(const at::Tensor& tok, const at::Tensor& wte, const at::Tensor& wpe, const at::Tensor& state,
+                  const at::Tensor& out) {
+  check_cuda(tok, "tok", I64);
+  check_cuda(wte, "wte", BF16);
+  check_cuda(wpe, "wpe", BF16);
+  TORCH_CHECK(wte.dim() == 2 && wpe.dim() == 2 && wte.size(1) == wpe.size(1) && wte.size(1) % 8 == 0,
+              "decode_embed: wte [Vp, C], wpe [n_pos, C], C % 8 == 0");
+  const int64_t B = tok.numel(), C = wte.size(1);
+  check_cuda(out, "out", BF16, B * C);
+  check_al16(wte, "wte");
+  check_al16(wpe, "wpe");
+  check_al16(out, "out");
+  check_state(state);
+  hip_check(pde_decode_embed(ptr<int64_t>(tok), wte.data_ptr(), wpe.data_ptr(), ptr<int>(state), out.data_ptr(), (int)B,
+                             (int)C, (int)wte.size(0), (int)wpe.size(0), cur_stream()),
+            "decode_embed");
+}
+
+void sample(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next, const at::Tensor& out,
+            const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k, int64_t eos,
+            const OptT& thr_out) {
+  check_cuda(logits, "logits", BF16);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) % 8 == 0, "sample: logits must be [B, Vp] with Vp % 8 == 0");
+  const int64_t B = logits.size(0), Vp = logits.size(1);
+  TORCH_CHECK(B >= 1 && B <= PDE_DS_MAX_ROWS, "sample: 1 <= B <= ", PDE_DS_MAX_ROWS, ", got ", B);
+  TORCH_CHECK(V >= 1 && V <= Vp, "sample: 1 <= V <= Vp");
+  TORCH_CHECK(top_k >= 0 && eos >= -1 && eos < V, "sample: top_k >= 0 and eos in [-1, V)");
+  check_al16(logits, "logits");
+  check_state(state);
+  check_cuda(next, "next", I64, B);
+  check_cuda(out, "out", I64);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == B && T0 >= 0 && T0 <= out.size(1), "sample: out must be [B, >= T0]");
+  PdeSample a{};
+  a.logits = logits.data_ptr();
+  a.state = ptr<int>(state);
+  a.next = ptr<int64_t>(next);
+  a.out = ptr<int64_t>(out);
+  a.logits_out = nullptr;
+  a.max_new = 0;
+  if (logits_out.has_value() && logits_out->defined()) {
+    check_cuda(*logits_out, "logits_out", BF16);
+    TORCH_CHECK(logits_out->dim() == 3 && logits_out->size(0) == B && logits_out->size(2) == V,
+                "sample: logits_out must be [B, max_new, V]");
+    a.logits_out = logits_out->data_ptr();
+    a.max_new = (int)logits_out->size(1);
+  }
+  a.thr_out = optr<int>(thr_out, "thr_out", I32, B);
+  a.B = (int)B;
+  a.V = (int)V;
+  a.Vp = (int)Vp;
+  a.T0 = (int)T0;
+  a.out_stride = (int)out.size(1);
+  a.inv_temp = (float)inv_temp;
+  a.greedy = greedy ? 1 : 0;
+  a.top_k = (int)top_k;
+  a.eos = (int)eos;
+  hip_check(pde_sample(a, cur_stream()), "sample");
+}
+
+}  // namespace
+
+void register_decode(pybind11::module& m) {
+  namespace py = pybind11;
+  m.def("skinny_splits", &skinny_splits);
+  m.def("skinny_linear", &skinny_linear, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"),
+        py::arg("part") = py::none(), py::arg("gelu") = false);
+  m.def("decode_attn_chunk", &decode_attn_chunk);
+  m.def("decode_attention", &decode_attention);
+  m.def("cache_fill", &cache_fill);
+  m.def("decode_embed", &decode_embed);
+  m.def("decode_sample", &sample, py::arg("logits"), py::arg("V"), py::arg("state"), py::arg("next"), py::arg("out"),
+        py::arg("logits_out"), py::arg("T0"), py::arg("inv_temp"), py::arg("greedy"), py::arg("top_k"), py::arg("eos"),
+        py::arg("thr_out") = py::none());
+  m.attr("DECODE_STATE_WORDS") = PDE_DS_WORDS;
+}
+
+}  // namespace pde

@@ -57,5 +57,6 @@ constexpr auto F64 = at::kDouble;
 // registration hooks of the extra binding units (called from PYBIND11_MODULE in ops_bindings.cpp)
 void register_transformer(pybind11::module& m);
 void register_resnet(pybind11::module& m);
+void register_decode(pybind11::module& m);
 
 }  // namespace pde

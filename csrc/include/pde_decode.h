@@ -1,0 +1,65 @@
+// extern "C" launchers of the GPT-2 decode kernels (csrc/kernels/decode.hip) and the layout of the
+// device-side decode state they share.
+//
+// Everything that changes from one generated token to the next lives in the state buffer, never in a
+// launch argument, so one captured decode step replays correctly for every token:
+//
+//   words 0..3   sampling RNG state {seed lo, seed hi, draw, stream}  (ops/rng.py DeviceRNG layout)
+//   word  4      position p of the token the next decode step embeds / attends from
+//   word  5      step: index of the next token to generate (output slot T0 + step)
+//   words 6, 7   reserved
+//   words 8..23  per-row "finished" flags (a row that has emitted eos keeps emitting it)
+//
+// The sampler launch reads the state; its one-thread tail kernel advances p, step and the draw number.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+#define PDE_DS_RNG 0
+#define PDE_DS_POS 4
+#define PDE_DS_STEP 5
+#define PDE_DS_FIN 8
+#define PDE_DS_MAX_ROWS 16
+#define PDE_DS_WORDS 24
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+// y[M, N] = x[M, K] W[N, K]^T (+ bias) (-> tanh-GELU), bf16, 1 <= M <= 16, K % 64 == 0, N % 8 == 0.
+// pde_skinny_splits(N, K) > 1 means the launch splits K over that many blocks per row tile and needs
+// `part`: splits * M * N floats (slabs summed in slab order by a second kernel).
+int pde_skinny_splits(int N, int K);
+hipError_t pde_skinny_linear(const void* x, const void* W, const void* bias, void* y, float* part, int M, int N, int K,
+                             int gelu, hipStream_t st);
+
+// keys per block of the decode attention (a constant of the kernel)
+int pde_decode_attn_chunk(void);
+// cache: one layer, [2][B][H][Tmax][64] bf16; qkv: [B, 3 * H * 64] c_attn output of the new token at position
+// p = state[PDE_DS_POS]; part: B * H * ceil(Tmax / chunk) * 66 floats; out: [B, H * 64]
+hipError_t pde_decode_attention(const void* qkv, void* cache, const int* state, float* part, void* out, int B, int H,
+                                int Tmax, float scale, hipStream_t st);
+// K and V of positions 0 .. T0-1 of a prefill c_attn output [B, Tpad, 3 * H * 64] -> one layer's cache
+hipError_t pde_cache_fill(const void* qkv, void* cache, int B, int H, int Tpad, int T0, int Tmax, hipStream_t st);
+// out[b] = wte[tok[b]] + wpe[p]
+hipError_t pde_decode_embed(const int64_t* tok, const void* wte, const void* wpe, const int* state, void* out, int B,
+                            int C, int Vp, int n_pos, hipStream_t st);
+
+typedef struct PdeSample {
+  const void* logits;   // [B, Vp] bf16
+  int* state;           // PDE_DS_WORDS
+  int64_t* next;        // [B]
+  int64_t* out;         // [B, out_stride]; token -> out[b, T0 + step]
+  void* logits_out;     // [B, max_new, V] bf16 or null
+  int* thr_out;         // [B] or null (tests): the top-k threshold as its 16-bit key, 0 without top-k
+  int B, V, Vp, T0, out_stride, max_new;
+  float inv_temp;       // fp32(1 / temperature); unused when greedy
+  int greedy;           // temperature == 0
+  int top_k;            // 0: all V
+  int eos;              // -1: none
+} PdeSample;
+hipError_t pde_sample(PdeSample a, hipStream_t st);
+
+#ifdef __cplusplus
+}
+#endif

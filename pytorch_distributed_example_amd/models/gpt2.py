@@ -13,6 +13,11 @@ kernels from a counter-based device RNG (``ops/rng.py``): ``GPT.rng`` draws one 
 forward, and every site of that forward and its backward regenerates its mask from it.  Sites are
 numbered: embedding 0; layer ``l`` attention probabilities ``1 + 3l``, attention-projection output
 ``2 + 3l``, MLP output ``3 + 3l``.
+
+Generation (``GPT.generate``): the prompt goes once through the training kernels and fills a KV cache;
+every further token is one decode step over ``ops/decode.py`` (``DecodeSession``) whose per-token state
+lives on the device, so the step is captured once and replayed.  It uses a ``DeviceRNG`` of its own, never
+``GPT.rng``.
 """
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn as tnn
 
+from ..ops import decode as D
 from ..ops import transformer as T
 from ..ops.rng import DeviceRNG
 
@@ -116,6 +122,32 @@ class Block(tnn.Module):
         x, h = T.add_layer_norm_residual(x, self.attn(h), self.ln_2.weight, self.ln_2.bias, self.ln_2.eps)
         return x, self.mlp(h)
 
+    def forward_deferred_qkv(self, x, delta=None):
+        """``forward_deferred`` without dropout that also returns this layer's c_attn output
+        ``[B, T, 3C]``: the prefill of ``GPT.generate`` fills the KV cache from it."""
+        if delta is None:
+            x, h = T.layer_norm_residual(x, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
+        else:
+            x, h = T.add_layer_norm_residual(x, delta, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
+        qkv = self.attn.c_attn(h)
+        a = self.attn.c_proj(T.causal_attention(qkv, self.attn.n_head))
+        x, h = T.add_layer_norm_residual(x, a, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps)
+        return x, self.mlp(h), qkv
+
+    def decode_deferred(self, x, delta, cache, state):
+        """One-token ``forward_deferred`` over the decode kernels: ``x`` / ``delta`` are ``[B, C]``, the
+        new K and V are appended to ``cache`` at the position held by ``state``."""
+        if delta is None:
+            x, h = T.layer_norm_residual(x, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
+        else:
+            x, h = T.add_layer_norm_residual(x, delta, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
+        qkv = D.skinny_linear(h, self.attn.c_attn.weight, self.attn.c_attn.bias)
+        a = D.decode_attention(qkv, cache, self.layer_idx, state)
+        a = D.skinny_linear(a, self.attn.c_proj.weight, self.attn.c_proj.bias)
+        x, h = T.add_layer_norm_residual(x, a, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps)
+        f = D.skinny_linear(h, self.mlp.c_fc.weight, self.mlp.c_fc.bias, gelu=True)
+        return x, D.skinny_linear(f, self.mlp.c_proj.weight, self.mlp.c_proj.bias)
+
     def _forward_deferred_drop(self, x, delta, snap):
         l, p = self.layer_idx, self.resid_pdrop
         if delta is None:
@@ -192,6 +224,91 @@ class GPT(tnn.Module):
             return T.lm_logits(x, t.wte.weight, self.config.vocab_size)
         return T.lm_head_loss(x, t.wte.weight, targets, self.config.vocab_size)
 
+    # ------------------------------------------------------------------------------- generation
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, seed=None, generator=None,
+                 eos_token_id=None, use_graph=True, return_logits=False, _after_prefill=None):
+        """Sample ``max_new_tokens`` tokens after the prompts ``idx`` ``[B, T0]`` (one length, ``T0 >= 1``).
+
+        Returns ``[B, T0 + max_new_tokens]`` int64, and with ``return_logits`` also the logits every token
+        was sampled from, ``[B, max_new_tokens, V]`` (bf16 on the GPU, the model's dtype on the CPU).
+        Sampling is defined in ``ops/decode.py``: ``temperature == 0`` is greedy (lowest index among equal
+        maxima), ``top_k`` keeps ties at its threshold.  The random numbers come from ``generator`` (a
+        ``DeviceRNG`` whose draw number advances by ``max_new_tokens``; checkpoint it with
+        ``state_dict()``) or a fresh one from ``seed``; ``model.rng``, the dropout generator, is never
+        touched.  A row that emits ``eos_token_id`` keeps emitting it.  Runs without gradients and with
+        dropout off, and restores the module's training flag.
+
+        GPU (bf16, ``B <= 16``): the prompt, padded to a multiple of 128, goes through the training
+        kernels once and fills the KV cache; every further token is one decode step -- about a hundred
+        small launches that read position, output slot, RNG draw and finished flags from a device state
+        buffer.  With ``use_graph`` that step is captured once and replayed per token: no host work and no
+        host read until the result.  CPU: the plain definition, a full forward per token.
+
+        ``T0 + max_new_tokens`` must not exceed ``block_size`` (learned absolute positions: no sliding
+        window)."""
+        cfg = self.config
+        if idx.dim() != 2 or idx.shape[1] < 1:
+            raise ValueError("generate: idx must be [B, T0] with T0 >= 1")
+        B, T0 = idx.shape
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens < 1:
+            raise ValueError("generate: max_new_tokens must be >= 1")
+        if T0 + max_new_tokens > cfg.block_size:
+            raise ValueError(f"generate: T0 + max_new_tokens = {T0 + max_new_tokens} exceeds block_size "
+                             f"{cfg.block_size} (positions are learned and absolute: no sliding window)")
+        if temperature < 0:
+            raise ValueError("generate: temperature must be >= 0")
+        if top_k is not None and top_k < 1:
+            raise ValueError("generate: top_k must be >= 1")
+        if eos_token_id is not None and not 0 <= eos_token_id < cfg.vocab_size:
+            raise ValueError("generate: eos_token_id must be a token of the vocabulary")
+        dev = self.transformer.wte.weight.device
+        if generator is None:
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            generator = DeviceRNG(seed, device=dev)
+        else:
+            generator.to(dev)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                run = self._generate_gpu if dev.type == "cuda" else self._generate_cpu
+                return run(idx.to(dev).long(), max_new_tokens, float(temperature), top_k, generator, eos_token_id,
+                           use_graph, return_logits, _after_prefill)
+        finally:
+            self.train(was_training)
+
+    def _generate_cpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill):
+        V = self.config.vocab_size
+        seq = idx
+        fin = torch.zeros(idx.shape[0], dtype=torch.bool)
+        kept = []
+        for _ in range(n_new):
+            logits = self(seq)[:, -1]
+            tok = D.sample_reference(logits, V, generator.next(), temperature, top_k)
+            if eos is not None:
+                tok = torch.where(fin, torch.full_like(tok, eos), tok)
+                fin = fin | (tok == eos)
+            seq = torch.cat([seq, tok[:, None]], dim=1)
+            if return_logits:
+                kept.append(logits)
+        return (seq, torch.stack(kept, dim=1)) if return_logits else seq
+
+    def _generate_gpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill):
+        ses = DecodeSession(self, idx, n_new, temperature, top_k, generator.state, eos, return_logits)
+        if _after_prefill is not None:
+            _after_prefill(ses.cache)
+        if n_new > 1 and use_graph:
+            graph = ses.capture()
+            for _ in range(n_new - 1):
+                graph.replay()
+        else:
+            for _ in range(n_new - 1):
+                ses.step()
+        generator.state.copy_(ses.state.rng)      # the draw number advanced by n_new, on the device
+        return (ses.out, ses.logits_out) if return_logits else ses.out
+
     def num_params(self, non_embedding: bool = False):
         n = sum(p.numel() for p in self.parameters())
         if non_embedding:
@@ -209,6 +326,84 @@ class GPT(tnn.Module):
         c = self.config
         N = self.num_params() - self.transformer.wpe.weight.numel()
         return 6 * N + 6 * c.n_layer * c.n_embd * c.block_size  # causal: half of 12*L*C*T
+
+
+class DecodeSession:
+    """One GPU generation of ``GPT.generate``: the KV cache, the device state and the static buffers.
+
+    The constructor runs the prefill -- the prompt, padded to a multiple of 128, through the training
+    kernels, filling the cache -- and samples the first token.  ``step()`` then generates one token per
+    call and touches nothing on the host that changes between tokens, so ``capture()`` can record it once
+    and every ``replay()`` of the returned graph yields the next token.  Call under ``torch.no_grad()``
+    with the model in eval mode (``GPT.generate`` does)."""
+
+    def __init__(self, model, idx, n_new, temperature=1.0, top_k=None, rng_state=None, eos=None,
+                 return_logits=False):
+        cfg, t = model.config, model.transformer
+        dev = idx.device
+        B, T0 = idx.shape
+        wte, wpe = t.wte.weight, t.wpe.weight
+        if B > D.MAX_ROWS:
+            raise NotImplementedError(f"generate: at most {D.MAX_ROWS} sequences on the GPU (got {B})")
+        if wte.dtype != torch.bfloat16:
+            raise NotImplementedError("generate: the GPU path is bf16")
+        Tpad = min(-(-T0 // 128) * 128, cfg.block_size)
+        if Tpad % 128:
+            raise NotImplementedError("generate: the prefill needs a window that is a multiple of 128 "
+                                      f"(block_size {cfg.block_size} caps it at {Tpad})")
+        self.model, self.T0, self.V = model, T0, cfg.vocab_size
+        self.sampling = (float(temperature), top_k, eos)
+        # prefill: the training kernels over the padded prompt (causal: the pad never reaches positions < T0)
+        self.cache = D.KVCache(cfg, B, T0 + n_new, dev)
+        idx_pad = torch.zeros(B, Tpad, device=dev, dtype=torch.int64)
+        idx_pad[:, :T0] = idx
+        x, delta = T.embedding(idx_pad, wte, wpe), None
+        for l, blk in enumerate(t.h):
+            x, delta, qkv = blk.forward_deferred_qkv(x, delta)
+            D.cache_fill(qkv, self.cache, l, T0)
+        # only row T0 - 1 goes through ln_f and the LM head: the [B * Tpad, Vp] logits are never formed
+        h = T.add_layer_norm_residual(x[:, T0 - 1].contiguous(), delta[:, T0 - 1].contiguous(),
+                                      t.ln_f.weight, t.ln_f.bias, t.ln_f.eps)[1]
+        self.state = D.DecodeState(dev, rng_state, pos=T0 - 1, step=0)
+        self.out = torch.zeros(B, T0 + n_new, device=dev, dtype=torch.int64)
+        self.out[:, :T0] = idx
+        self.next = torch.zeros(B, device=dev, dtype=torch.int64)
+        self.logits_out = (torch.empty(B, n_new, self.V, device=dev, dtype=torch.bfloat16)
+                           if return_logits else None)
+        self._sample(D.skinny_linear(h, wte))      # token T0; the state now points at it
+
+    def _sample(self, logits):
+        temperature, top_k, eos = self.sampling
+        D.sample(logits, self.V, self.state, temperature, top_k, eos, next=self.next, out=self.out,
+                 logits_out=self.logits_out, T0=self.T0)
+
+    def step(self):
+        """embedding -> blocks (residual adds deferred into the next LayerNorm) -> ln_f -> LM head -> sampler"""
+        t = self.model.transformer
+        x, delta = D.decode_embed(self.next, t.wte.weight, t.wpe.weight, self.state), None
+        for blk in t.h:
+            x, delta = blk.decode_deferred(x, delta, self.cache, self.state)
+        h = T.add_layer_norm_residual(x, delta, t.ln_f.weight, t.ln_f.bias, t.ln_f.eps)[1]
+        self._sample(D.skinny_linear(h, t.wte.weight))
+
+    def capture(self):
+        """The step as a graph.  An eager warm-up step runs first on a side stream and is undone by restoring
+        the state it advanced (the cache row and output slot it wrote are written again, identically, by
+        the first replay)."""
+        dev = self.next.device
+        saved = (self.state.buf.clone(), self.next.clone())
+        cur = torch.cuda.current_stream(dev)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            self.step()
+        cur.wait_stream(side)
+        self.state.buf.copy_(saved[0])
+        self.next.copy_(saved[1])
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self.step()
+        return graph
 
 
 def build_gpt2(cfg: GPTConfig = None, seed: int = 0, device=None, dtype=torch.bfloat16) -> GPT:

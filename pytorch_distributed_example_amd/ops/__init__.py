@@ -12,6 +12,9 @@ from . import generic  # noqa: F401
 from . import transformer  # noqa: F401
 from . import rng  # noqa: F401
 from .rng import DeviceRNG, dropout_mask, effective_p  # noqa: F401
+from . import decode  # noqa: F401
+from .decode import (DecodeState, KVCache, decode_attention, sample, sample_reference,  # noqa: F401
+                     skinny_linear)
 
 
 def linear(x, weight, bias=None):

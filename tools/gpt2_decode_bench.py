@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""GPT-2 small generation speed: ms per token of the KV-cache decode step in graph replay, against the
+only way to generate without it -- ``model(window)[:, -1]``, a full forward over the context per token.
+
+Per batch size (1 and 16) and 512 tokens of context, in one process:
+
+* decode: a ``DecodeSession`` is prefilled with a 512-token prompt, its step is captured once, and windows
+  of ``--window`` replays are timed (device events around the window and around every replay; the state is
+  put back to position 512 before each window, so the context stays 512 .. 512 + window - 1).  The same
+  step is also timed eagerly (host-launched) for comparison.
+* recompute: ``model(idx[B, 512])[:, -1]`` eagerly under ``no_grad``, one event pair per call.
+
+Achieved bytes/s of the decode step = (every parameter once in bf16, ``wte`` only through the LM head,
+plus the K and V rows read, mean over the window) / median ms per token; compared with the 6.29 TB/s
+achievable HBM bandwidth of MI355X_MICROARCH.md.  One JSON line per batch size.
+
+    python tools/gpt2_decode_bench.py [--context 512] [--window 64] [--rounds 5] [--batch-sizes 1 16]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from pytorch_distributed_example_amd.models import GPTConfig, build_gpt2  # noqa: E402
+from pytorch_distributed_example_amd.models.gpt2 import DecodeSession  # noqa: E402
+from pytorch_distributed_example_amd.ops import DeviceRNG  # noqa: E402
+
+HBM_BYTES_PER_S = 6.29e12
+
+
+def events(n):
+    return [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+
+
+def bench_decode(model, idx, a):
+    ses = DecodeSession(model, idx, a.window + 1, 1.0, 50, DeviceRNG(0, device=idx.device).state)
+    graph = ses.capture()
+    start = (ses.state.buf.clone(), ses.next.clone())
+
+    def rewind():
+        ses.state.buf.copy_(start[0])
+        ses.next.copy_(start[1])
+
+    per_replay, per_window, eager = [], [], []
+    for r in range(a.rounds + 1):                       # round 0 is warm-up
+        rewind()
+        ev, (w0, w1) = events(a.window), events(1)[0]
+        torch.cuda.synchronize()
+        w0.record()
+        for s, e in ev:
+            s.record()
+            graph.replay()
+            e.record()
+        w1.record()
+        torch.cuda.synchronize()
+        if r:
+            per_replay += [s.elapsed_time(e) for s, e in ev]
+            per_window.append(w0.elapsed_time(w1) / a.window)
+        rewind()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.window):
+            ses.step()
+        torch.cuda.synchronize()
+        if r:
+            eager.append((time.perf_counter() - t0) * 1e3 / a.window)
+    return per_replay, per_window, eager
+
+
+def bench_recompute(model, idx, reps):
+    for _ in range(3):
+        model(idx)[:, -1]
+    ev = events(reps)
+    torch.cuda.synchronize()
+    for s, e in ev:
+        s.record()
+        model(idx)[:, -1]
+        e.record()
+    torch.cuda.synchronize()
+    return [s.elapsed_time(e) for s, e in ev]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--context", type=int, default=512)
+    ap.add_argument("--window", type=int, default=64)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--recompute-reps", type=int, default=20)
+    ap.add_argument("--batch-sizes", type=int, nargs="+", default=[1, 16])
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("gpt2_decode_bench: needs a GPU (no CPU fallback: a CPU time says nothing about the kernels)")
+    dev = torch.device("cuda", 0)
+    cfg = GPTConfig()
+    model = build_gpt2(cfg, seed=0, device=dev).eval()
+    weight_bytes = 2 * sum(p.numel() for p in model.parameters())
+    with torch.no_grad():
+        for B in a.batch_sizes:
+            idx = torch.randint(0, cfg.vocab_size, (B, a.context), device=dev,
+                                generator=torch.Generator(dev).manual_seed(B))
+            per_replay, per_window, eager = bench_decode(model, idx, a)
+            rec = bench_recompute(model, idx, a.recompute_reps)
+            mean_keys = a.context + (a.window + 1) / 2.0          # keys read at positions context .. context+window-1
+            kv_bytes = cfg.n_layer * 2 * B * cfg.n_head * mean_keys * 64 * 2
+            ms = statistics.median(per_replay)
+            bps = (weight_bytes + kv_bytes) / (ms * 1e-3)
+            print(json.dumps({
+                "metric": "gpt2_small_decode_ms_per_token", "batch_size": B, "context": a.context,
+                "window": a.window, "rounds": a.rounds,
+                "decode_graph_ms_per_token": {"median": round(ms, 4), "min": round(min(per_replay), 4),
+                                              "max": round(max(per_replay), 4),
+                                              "window_mean_median": round(statistics.median(per_window), 4)},
+                "decode_eager_ms_per_token_median": round(statistics.median(eager), 4),
+                "recompute_forward_ms_per_token": {"median": round(statistics.median(rec), 4),
+                                                   "min": round(min(rec), 4), "max": round(max(rec), 4)},
+                "speedup_vs_recompute": round(statistics.median(rec) / ms, 2),
+                "tokens_per_s_decode": round(B / (ms * 1e-3), 1),
+                "bytes_per_token": {"weights": weight_bytes, "kv": int(kv_bytes)},
+                "achieved_bytes_per_s": round(bps, 1),
+                "share_of_6.29TBps": round(bps / HBM_BYTES_PER_S, 4)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
