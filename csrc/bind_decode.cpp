@@ -56,6 +56,7 @@ void decode_attention(const at::Tensor& qkv, const at::Tensor& cache, const at::
                       const at::Tensor& out, int64_t H, double scale) {
   TORCH_CHECK(qkv.dim() == 2 && H >= 1 && qkv.size(1) == 3 * H * 64, "decode_attention: qkv must be [B, 3 * H * 64]");
   const int64_t B = qkv.size(0);
+  TORCH_CHECK(B >= 1 && B <= PDE_DS_MAX_ROWS, "decode_attention: 1 <= B <= ", PDE_DS_MAX_ROWS, ", got ", B);
   check_cuda(qkv, "qkv", BF16);
   check_al16(qkv, "qkv");
   check_cache(cache, B, H);
@@ -88,6 +89,7 @@ void decode_embed(const at::Tensor& tok, const at::Tensor& wte, const at::Tensor
   TORCH_CHECK(wte.dim() == 2 && wpe.dim() == 2 && wte.size(1) == wpe.size(1) && wte.size(1) % 8 == 0,
               "decode_embed: wte [Vp, C], wpe [n_pos, C], C % 8 == 0");
   const int64_t B = tok.numel(), C = wte.size(1);
+  TORCH_CHECK(B >= 1 && B <= PDE_DS_MAX_ROWS, "decode_embed: 1 <= B <= ", PDE_DS_MAX_ROWS, ", got ", B);
   check_cuda(out, "out", BF16, B * C);
   check_al16(wte, "wte");
   check_al16(wpe, "wpe");
@@ -100,13 +102,14 @@ void decode_embed(const at::Tensor& tok, const at::Tensor& wte, const at::Tensor
 
 void sample(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next, const at::Tensor& out,
             const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k, int64_t eos,
-            const OptT& thr_out) {
+            const OptT& thr_out, double top_p) {
   check_cuda(logits, "logits", BF16);
   TORCH_CHECK(logits.dim() == 2 && logits.size(1) % 8 == 0, "sample: logits must be [B, Vp] with Vp % 8 == 0");
   const int64_t B = logits.size(0), Vp = logits.size(1);
   TORCH_CHECK(B >= 1 && B <= PDE_DS_MAX_ROWS, "sample: 1 <= B <= ", PDE_DS_MAX_ROWS, ", got ", B);
   TORCH_CHECK(V >= 1 && V <= Vp, "sample: 1 <= V <= Vp");
   TORCH_CHECK(top_k >= 0 && eos >= -1 && eos < V, "sample: top_k >= 0 and eos in [-1, V)");
+  TORCH_CHECK(top_p >= 0.0 && top_p <= 1.0, "sample: top_p in [0, 1] (0 and 1: off), got ", top_p);
   check_al16(logits, "logits");
   check_state(state);
   check_cuda(next, "next", I64, B);
@@ -136,6 +139,7 @@ void sample(const at::Tensor& logits, int64_t V, const at::Tensor& state, const 
   a.greedy = greedy ? 1 : 0;
   a.top_k = (int)top_k;
   a.eos = (int)eos;
+  a.top_p = top_p;
   hip_check(pde_sample(a, cur_stream()), "sample");
 }
 
@@ -152,7 +156,7 @@ void register_decode(pybind11::module& m) {
   m.def("decode_embed", &decode_embed);
   m.def("decode_sample", &sample, py::arg("logits"), py::arg("V"), py::arg("state"), py::arg("next"), py::arg("out"),
         py::arg("logits_out"), py::arg("T0"), py::arg("inv_temp"), py::arg("greedy"), py::arg("top_k"), py::arg("eos"),
-        py::arg("thr_out") = py::none());
+        py::arg("thr_out") = py::none(), py::arg("top_p") = 0.0);
   m.attr("DECODE_STATE_WORDS") = PDE_DS_WORDS;
 }
 

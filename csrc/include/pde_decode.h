@@ -9,6 +9,9 @@
 //   word  5      step: index of the next token to generate (output slot T0 + step)
 //   words 6, 7   reserved
 //   words 8..23  per-row "finished" flags (a row that has emitted eos keeps emitting it)
+//   words 24..39 per-row position offsets off_b = len_b - max(len) <= 0 of a ragged prompt batch, constant
+//                for the whole generation: row b is at position p + off_b and its output slot is
+//                T0 + off_b + step, with T0 = max(len) the launch argument.  All zero: one prompt length.
 //
 // The sampler launch reads the state; its one-thread tail kernel advances p, step and the draw number.
 #pragma once
@@ -20,7 +23,8 @@
 #define PDE_DS_STEP 5
 #define PDE_DS_FIN 8
 #define PDE_DS_MAX_ROWS 16
-#define PDE_DS_WORDS 24
+#define PDE_DS_OFF 24
+#define PDE_DS_WORDS 40
 
 #ifdef __cplusplus
 extern "C" {
@@ -35,13 +39,14 @@ hipError_t pde_skinny_linear(const void* x, const void* W, const void* bias, voi
 
 // keys per block of the decode attention (a constant of the kernel)
 int pde_decode_attn_chunk(void);
-// cache: one layer, [2][B][H][Tmax][64] bf16; qkv: [B, 3 * H * 64] c_attn output of the new token at position
-// p = state[PDE_DS_POS]; part: B * H * ceil(Tmax / chunk) * 66 floats; out: [B, H * 64]
+// cache: one layer, [2][B][H][Tmax][64] bf16; qkv: [B, 3 * H * 64] c_attn output of the new token, row b at
+// position p_b = state[PDE_DS_POS] + state[PDE_DS_OFF + b] (B <= PDE_DS_MAX_ROWS);
+// part: B * H * ceil(Tmax / chunk) * 66 floats; out: [B, H * 64]
 hipError_t pde_decode_attention(const void* qkv, void* cache, const int* state, float* part, void* out, int B, int H,
                                 int Tmax, float scale, hipStream_t st);
 // K and V of positions 0 .. T0-1 of a prefill c_attn output [B, Tpad, 3 * H * 64] -> one layer's cache
 hipError_t pde_cache_fill(const void* qkv, void* cache, int B, int H, int Tpad, int T0, int Tmax, hipStream_t st);
-// out[b] = wte[tok[b]] + wpe[p]
+// out[b] = wte[tok[b]] + wpe[p_b]
 hipError_t pde_decode_embed(const int64_t* tok, const void* wte, const void* wpe, const int* state, void* out, int B,
                             int C, int Vp, int n_pos, hipStream_t st);
 
@@ -49,14 +54,16 @@ typedef struct PdeSample {
   const void* logits;   // [B, Vp] bf16
   int* state;           // PDE_DS_WORDS
   int64_t* next;        // [B]
-  int64_t* out;         // [B, out_stride]; token -> out[b, T0 + step]
+  int64_t* out;         // [B, out_stride]; token -> out[b, T0 + off_b + step]
   void* logits_out;     // [B, max_new, V] bf16 or null
-  int* thr_out;         // [B] or null (tests): the top-k threshold as its 16-bit key, 0 without top-k
+  int* thr_out;         // [B] or null (tests): the effective threshold (top-k, raised by top-p) as its 16-bit
+                        // key, 0 with neither
   int B, V, Vp, T0, out_stride, max_new;
   float inv_temp;       // fp32(1 / temperature); unused when greedy
   int greedy;           // temperature == 0
   int top_k;            // 0: all V
   int eos;              // -1: none
+  double top_p;         // nucleus mass in (0, 1); 0 or >= 1: off.  Unused when greedy
 } PdeSample;
 hipError_t pde_sample(PdeSample a, hipStream_t st);
 

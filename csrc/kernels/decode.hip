@@ -21,7 +21,12 @@
 //                   per-call reset, and the sum order is the slab / chunk index by construction.
 //   sampler         one block per row; radix select (2 x 8 bits) for the top-k threshold, Gumbel-max with
 //                   Philox words addressed as pde_rng::group_words; a one-thread tail kernel advances the
-//                   state after every row has read it.
+//                   state after every row has read it.  Top-p is a second radix select over the same key,
+//                   weighted by exp(z - z_max) in 64-bit fixed point: integer LDS atomics sum in any order
+//                   to the same bits, which float atomics would not.  It is a template instantiation of
+//                   its own, so the sampler without top-p is the code it was.
+//   ragged batches  row b sits at position p_b = state position + state offset of row b; every block of
+//                   the attention, the embedding and the sampler derives what it does from its own p_b.
 #include "pde_hip.h"
 #include "pde_bf16.h"
 #include "pde_act.h"
@@ -121,18 +126,20 @@ __global__ __launch_bounds__(256) void k_skinny_combine(const float* __restrict_
 constexpr int DC_CH = 128;      // keys per block
 constexpr int DC_PART = 66;     // floats per partial: max, sum, 64 outputs
 
-// grid (chunks of Tmax, B * H), block 256.  Scores: thread pair (2j, 2j + 1) holds the two 32-dim halves of
+// grid (chunks of Tmax, H, B), block 256 (b is a grid index of its own, so the row's state words can be
+// loaded before any other arithmetic).  Scores: thread pair (2j, 2j + 1) holds the two 32-dim halves of
 // key c * 128 + j.  Outputs: thread (kg = tid >> 3, dg = tid & 7) holds dims 8 dg.. of keys kg + 32 i.  Every
 // K / V row comes straight from global memory to VGPRs, all loads issued before the first use.  Row p (the
-// new token) is taken from the c_attn row and written to the cache by the block whose chunk holds p.
+// new token; p = p_b, the position of batch row b) is taken from the c_attn row and written to the cache by
+// the block whose chunk holds p.  Blocks of chunks past p return: the grid is sized by Tmax.
 __global__ __launch_bounds__(256) void k_dec_attn(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ cache,
                                                   const int* __restrict__ state, float* __restrict__ part, int B, int H,
                                                   int Tmax, int nch, float scale) {
   __shared__ float ps[DC_CH];
   __shared__ float ored[32][64];
   __shared__ float wred[2][4];
-  const int c = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H;
-  const int p = state[PDE_DS_POS];
+  const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z, bh = b * H + h;
+  const int p = state[PDE_DS_POS] + state[PDE_DS_OFF + b];
   if (p < 0 || p >= Tmax || c * DC_CH > p) return;      // uniform per block
   const int C = H * 64, tid = threadIdx.x, w = tid >> 6;
   const bf16_t* row = qkv + (size_t)b * 3 * C + h * 64;  // q; + C: k; + 2C: v
@@ -212,11 +219,11 @@ __global__ __launch_bounds__(256) void k_dec_attn(const bf16_t* __restrict__ qkv
   }
 }
 
-// grid B * H, block 64: the partials of chunks 0 .. p / 128 in chunk order
+// grid (H, B), block 64: the partials of chunks 0 .. p_b / 128 in chunk order
 __global__ __launch_bounds__(64) void k_dec_attn_combine(const float* __restrict__ part, const int* __restrict__ state,
                                                          bf16_t* __restrict__ out, int H, int Tmax, int nch) {
-  const int bh = blockIdx.x, b = bh / H, h = bh % H, d = threadIdx.x;
-  const int p = state[PDE_DS_POS];
+  const int h = blockIdx.x, b = blockIdx.y, bh = b * H + h, d = threadIdx.x;
+  const int p = state[PDE_DS_POS] + state[PDE_DS_OFF + b];
   if (p < 0 || p >= Tmax) return;
   const int nact = p / DC_CH + 1;
   const float* src = part + (size_t)bh * nch * DC_PART;
@@ -250,15 +257,13 @@ __global__ __launch_bounds__(256) void k_cache_fill(const bf16_t* __restrict__ q
   *reinterpret_cast<uint4*>(cache + ((((size_t)kv * B + b) * H + h) * Tmax + t) * 64 + ch * 8) = v;
 }
 
-// thread per 8 elements of out [B, C]
+// grid (blocks of a row, B): thread per 8 elements of out[b, :]
 __global__ __launch_bounds__(256) void k_dec_embed(const int64_t* __restrict__ tok, const bf16_t* __restrict__ wte,
                                                    const bf16_t* __restrict__ wpe, const int* __restrict__ state,
                                                    bf16_t* __restrict__ out, int B, int C, int Vp, int n_pos) {
-  const int i = blockIdx.x * 256 + threadIdx.x, c8 = C >> 3;
-  if (i >= B * c8) return;
-  const int p = state[PDE_DS_POS];
-  if (p < 0 || p >= n_pos) return;
-  const int b = i / c8, c = (i % c8) * 8;
+  const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, c = i * 8;
+  const int p = state[PDE_DS_POS] + state[PDE_DS_OFF + b];
+  if (b >= B || c >= C || p < 0 || p >= n_pos) return;
   int64_t id = tok[b];
   id = id < 0 ? 0 : (id >= Vp ? Vp - 1 : id);
   float a[8], e[8];
@@ -323,9 +328,127 @@ __device__ __forceinline__ void radix_pick(const uint32_t (*hist)[256], uint32_t
   }
 }
 
+// wave 0, weighted form: the bin (counting from bin 255 down) at which the running mass first reaches
+// `target`, and the part of the target that bin has to cover.  whist: [4 waves][256 bins] of fixed-point mass;
+// 1 <= target <= total mass, so exactly one lane writes.  wsel[0] = bin, wsel[1] = target left
+__device__ __forceinline__ void radix_pick_mass(const uint64_t (*whist)[256], uint64_t target, uint64_t* wsel) {
+  const int l = threadIdx.x;    // 0..63
+  uint64_t cnt[4], c = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    cnt[q] = whist[0][4 * l + q] + whist[1][4 * l + q] + whist[2][4 * l + q] + whist[3][4 * l + q];
+    c += cnt[q];
+  }
+  uint64_t s = c;               // suffix sum over lanes >= l
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t lo = __shfl_down((uint32_t)s, o, 64), hi = __shfl_down((uint32_t)(s >> 32), o, 64);
+    if (l + o < 64) s += ((uint64_t)hi << 32) | lo;
+  }
+  const uint64_t excl = s - c;
+  if (excl < target && target <= s) {
+    uint64_t rem = target - excl;
+    int bin = 4 * l;
+#pragma unroll
+    for (int q = 3; q >= 0; --q) {
+      if (rem <= cnt[q]) {
+        bin = 4 * l + q;
+        break;
+      }
+      rem -= cnt[q];
+    }
+    wsel[0] = (uint64_t)bin;
+    wsel[1] = rem;
+  }
+}
+
+// 2^40 * exp(z - zmax), rounded: the mass of one candidate in fixed point (z <= zmax, so at most 2^40)
+__device__ __forceinline__ uint64_t mass_fx(float z, float zmax) {
+  return (uint64_t)rintf(expf(z - zmax) * 1099511627776.0f);
+}
+
+// The nucleus stage: among the candidates (key16 >= thr) the key of the largest logit value t with
+// mass{logit >= t} >= top_p * total mass.  Same two 8-bit passes as the top-k select, with every candidate
+// counted by its mass; the sums are integers, so the result does not depend on the order of the atomics.
+// All threads of the block call it; whist / wsel / wmax are its LDS.
+__device__ __forceinline__ uint32_t nucleus_threshold(const bf16_t* __restrict__ row, int V, int ngrp, uint32_t thr,
+                                                      float inv_temp, double top_p, uint64_t (*whist)[256],
+                                                      uint64_t* wsel, uint32_t* wmax, int nthreads) {
+  const int tid = threadIdx.x, w = tid >> 6;
+  if (tid == 0) wsel[0] = wsel[1] = 0ull;     // a row of NaNs has no mass and picks nothing: key 0 then
+  // the largest key of the row: always a candidate, and z is monotone in the key (inv_temp > 0)
+  uint32_t mk = 0;
+  for (int gi = tid; gi < ngrp; gi += nthreads) {
+    const uint2 w2 = reinterpret_cast<const uint2*>(row)[gi];
+    const uint32_t u[4] = {w2.x & 0xffffu, w2.x >> 16, w2.y & 0xffffu, w2.y >> 16};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const uint32_t key = 4 * gi + e < V ? key16(u[e]) : 0u;
+      mk = key > mk ? key : mk;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t t = __shfl_xor(mk, o, 64);
+    mk = t > mk ? t : mk;
+  }
+  if ((tid & 63) == 0) wmax[w] = mk;
+  __syncthreads();
+  for (int i = 0; i < nthreads / 64; ++i) mk = wmax[i] > mk ? wmax[i] : mk;
+  const uint32_t mbits = (mk & 0x8000u) ? (mk & 0x7fffu) : (~mk & 0xffffu);     // key16 inverted
+  const float zmax = bf2f(mbits) * inv_temp;
+
+  uint32_t hi = 0;
+  uint64_t target = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int i = tid; i < 1024; i += nthreads) (&whist[0][0])[i] = 0ull;
+    __syncthreads();
+    for (int gi = tid; gi < ngrp; gi += nthreads) {
+      const uint2 w2 = reinterpret_cast<const uint2*>(row)[gi];
+      const uint32_t u[4] = {w2.x & 0xffffu, w2.x >> 16, w2.y & 0xffffu, w2.y >> 16};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (4 * gi + e >= V) continue;
+        const uint32_t key = key16(u[e]);
+        if (key < thr) continue;
+        if (pass == 0) atomicAdd((unsigned long long*)&whist[w & 3][key >> 8],
+                                 (unsigned long long)mass_fx(bf2f(u[e]) * inv_temp, zmax));
+        else if ((key >> 8) == hi) atomicAdd((unsigned long long*)&whist[w & 3][key & 0xffu],
+                                             (unsigned long long)mass_fx(bf2f(u[e]) * inv_temp, zmax));
+      }
+    }
+    __syncthreads();
+    if (pass == 0) {
+      if (tid < 64) {          // total mass -> target, by every lane of wave 0 alike
+        uint64_t c = 0;
+        for (int q = 0; q < 4; ++q)
+          c += whist[0][4 * tid + q] + whist[1][4 * tid + q] + whist[2][4 * tid + q] + whist[3][4 * tid + q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const uint32_t lo = __shfl_xor((uint32_t)c, o, 64), h2 = __shfl_xor((uint32_t)(c >> 32), o, 64);
+          c += ((uint64_t)h2 << 32) | lo;
+        }
+        uint64_t t = (uint64_t)ceil(top_p * (double)c);
+        t = t < 1 ? 1 : (t > c ? c : t);
+        radix_pick_mass(whist, t, wsel);
+      }
+    } else if (w == 0) {
+      radix_pick_mass(whist, target, wsel);
+    }
+    __syncthreads();
+    if (pass == 0) {
+      hi = (uint32_t)wsel[0];
+      target = wsel[1];
+    }
+    __syncthreads();
+  }
+  return (hi << 8) | (uint32_t)wsel[0];
+}
+
 // grid B, block SM_NT (16 waves: a row of 50304 logits is ~50 per thread and pass; the 4 histograms are
-// shared by waves w, w + 4, ...)
+// shared by waves w, w + 4, ...).  TOPP adds the nucleus stage between the top-k select and the Gumbel pass.
 constexpr int SM_NT = 1024;
+template <bool TOPP>
 __global__ __launch_bounds__(SM_NT) void k_sample(PdeSample a) {
   __shared__ uint32_t hist[4][256];
   __shared__ uint32_t sel[2];
@@ -336,6 +459,7 @@ __global__ __launch_bounds__(SM_NT) void k_sample(PdeSample a) {
                           (uint32_t)a.state[PDE_DS_RNG + 2], (uint32_t)a.state[PDE_DS_RNG + 3]};
   const int step = a.state[PDE_DS_STEP];
   const int fin = a.state[PDE_DS_FIN + b];
+  const int slot = a.T0 + a.state[PDE_DS_OFF + b] + step;      // read here, with the other state words
   const int V = a.V, ngrp = a.Vp >> 2;
 
   uint32_t thr = 0;             // candidates: key16 >= thr
@@ -365,6 +489,14 @@ __global__ __launch_bounds__(SM_NT) void k_sample(PdeSample a) {
         thr = (hi << 8) | sel[0];
       }
       __syncthreads();
+    }
+  }
+  if constexpr (TOPP) {
+    if (!a.greedy) {
+      __shared__ uint64_t whist[4][256];
+      __shared__ uint64_t wsel[2];
+      __shared__ uint32_t wmax[SM_NT / 64];
+      thr = nucleus_threshold(row, V, ngrp, thr, a.inv_temp, a.top_p, whist, wsel, wmax, SM_NT);
     }
   }
 
@@ -415,7 +547,7 @@ __global__ __launch_bounds__(SM_NT) void k_sample(PdeSample a) {
     }
     a.next[b] = tok;
     if (a.thr_out) a.thr_out[b] = (int)thr;
-    if (step >= 0 && a.T0 + step < a.out_stride) a.out[(size_t)b * a.out_stride + a.T0 + step] = tok;
+    if (step >= 0 && slot >= 0 && slot < a.out_stride) a.out[(size_t)b * a.out_stride + slot] = tok;
   }
   if (a.logits_out && step >= 0 && step < a.max_new) {
     bf16_t* dst = reinterpret_cast<bf16_t*>(a.logits_out) + ((size_t)b * a.max_new + step) * V;
@@ -473,12 +605,12 @@ int pde_decode_attn_chunk(void) { return DC_CH; }
 
 hipError_t pde_decode_attention(const void* qkv, void* cache, const int* state, float* part, void* out, int B, int H,
                                 int Tmax, float scale, hipStream_t st) {
-  if (B < 1 || H < 1 || Tmax < 1) return hipErrorInvalidValue;
+  if (B < 1 || B > PDE_DS_MAX_ROWS || H < 1 || Tmax < 1) return hipErrorInvalidValue;
   const int nch = (Tmax + DC_CH - 1) / DC_CH;
-  hipLaunchKernelGGL(k_dec_attn, dim3(nch, B * H), dim3(256), 0, st, (const bf16_t*)qkv, (bf16_t*)cache, state, part, B,
+  hipLaunchKernelGGL(k_dec_attn, dim3(nch, H, B), dim3(256), 0, st, (const bf16_t*)qkv, (bf16_t*)cache, state, part, B,
                      H, Tmax, nch, scale);
   PDE_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_dec_attn_combine, dim3(B * H), dim3(64), 0, st, (const float*)part, state, (bf16_t*)out, H, Tmax,
+  hipLaunchKernelGGL(k_dec_attn_combine, dim3(H, B), dim3(64), 0, st, (const float*)part, state, (bf16_t*)out, H, Tmax,
                      nch);
   return hipGetLastError();
 }
@@ -493,17 +625,20 @@ hipError_t pde_cache_fill(const void* qkv, void* cache, int B, int H, int Tpad, 
 
 hipError_t pde_decode_embed(const int64_t* tok, const void* wte, const void* wpe, const int* state, void* out, int B,
                             int C, int Vp, int n_pos, hipStream_t st) {
-  if (B < 1 || C < 8 || C % 8 != 0 || Vp < 1 || n_pos < 1) return hipErrorInvalidValue;
-  const int n = B * (C / 8);
-  hipLaunchKernelGGL(k_dec_embed, dim3((n + 255) / 256), dim3(256), 0, st, tok, (const bf16_t*)wte, (const bf16_t*)wpe,
-                     state, (bf16_t*)out, B, C, Vp, n_pos);
+  if (B < 1 || B > PDE_DS_MAX_ROWS || C < 8 || C % 8 != 0 || Vp < 1 || n_pos < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_dec_embed, dim3((C / 8 + 255) / 256, B), dim3(256), 0, st, tok, (const bf16_t*)wte,
+                     (const bf16_t*)wpe, state, (bf16_t*)out, B, C, Vp, n_pos);
   return hipGetLastError();
 }
 
 hipError_t pde_sample(PdeSample a, hipStream_t st) {
   if (a.B < 1 || a.B > PDE_DS_MAX_ROWS || a.V < 1 || a.V > a.Vp || a.Vp % 8 != 0 || a.top_k < 0)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_sample, dim3(a.B), dim3(SM_NT), 0, st, a);
+  if (!(a.top_p >= 0.0)) return hipErrorInvalidValue;
+  if (!a.greedy && a.top_p > 0.0 && a.top_p < 1.0)
+    hipLaunchKernelGGL(k_sample<true>, dim3(a.B), dim3(SM_NT), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_sample<false>, dim3(a.B), dim3(SM_NT), 0, st, a);
   PDE_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_dec_advance, dim3(1), dim3(64), 0, st, a.state);
   return hipGetLastError();

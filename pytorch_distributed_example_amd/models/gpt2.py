@@ -226,13 +226,24 @@ class GPT(tnn.Module):
 
     # ------------------------------------------------------------------------------- generation
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, seed=None, generator=None,
-                 eos_token_id=None, use_graph=True, return_logits=False, _after_prefill=None):
-        """Sample ``max_new_tokens`` tokens after the prompts ``idx`` ``[B, T0]`` (one length, ``T0 >= 1``).
+                 eos_token_id=None, use_graph=True, return_logits=False, top_p=None, prompt_lens=None,
+                 pad_token_id=0, _after_prefill=None):
+        """Sample ``max_new_tokens`` tokens after the prompts ``idx`` ``[B, T0]`` (``T0 >= 1``).
 
         Returns ``[B, T0 + max_new_tokens]`` int64, and with ``return_logits`` also the logits every token
-        was sampled from, ``[B, max_new_tokens, V]`` (bf16 on the GPU, the model's dtype on the CPU).
-        Sampling is defined in ``ops/decode.py``: ``temperature == 0`` is greedy (lowest index among equal
-        maxima), ``top_k`` keeps ties at its threshold.  The random numbers come from ``generator`` (a
+        was sampled from, ``[B, max_new_tokens, V]`` indexed by step (bf16 on the GPU, the model's dtype on
+        the CPU).  Sampling is defined in ``ops/decode.py``: ``temperature == 0`` is greedy (lowest index
+        among equal maxima), ``top_k`` keeps ties at its threshold, and ``top_p`` in ``(0, 1]`` (``None`` and
+        1.0: off; ignored when greedy) then keeps the smallest set of largest logit values, ties kept, whose
+        mass inside the top-k set reaches ``top_p``.
+
+        ``prompt_lens`` (a list or int tensor of ``B`` lengths, read once on the host) makes the batch
+        ragged: ``idx`` is right-padded, row ``b``'s prompt is ``idx[b, :len_b]`` with
+        ``1 <= len_b <= T0`` and whatever lies beyond is ignored.  Every row starts at position 0 and
+        generates exactly ``max_new_tokens`` tokens at positions ``len_b .. len_b + max_new_tokens - 1``; in
+        the output they follow the prompt directly, and the rest of the row is ``pad_token_id``.  No
+        attention mask is involved: attention is causal, so a pad column never reaches a real position.
+        One RNG draw number per generated token, whatever the lengths.  The random numbers come from ``generator`` (a
         ``DeviceRNG`` whose draw number advances by ``max_new_tokens``; checkpoint it with
         ``state_dict()``) or a fresh one from ``seed``; ``model.rng``, the dropout generator, is never
         touched.  A row that emits ``eos_token_id`` keeps emitting it.  Runs without gradients and with
@@ -244,8 +255,8 @@ class GPT(tnn.Module):
         buffer.  With ``use_graph`` that step is captured once and replayed per token: no host work and no
         host read until the result.  CPU: the plain definition, a full forward per token.
 
-        ``T0 + max_new_tokens`` must not exceed ``block_size`` (learned absolute positions: no sliding
-        window)."""
+        ``T0 + max_new_tokens`` (``max(prompt_lens) + max_new_tokens`` for a ragged batch) must not exceed
+        ``block_size`` (learned absolute positions: no sliding window)."""
         cfg = self.config
         if idx.dim() != 2 or idx.shape[1] < 1:
             raise ValueError("generate: idx must be [B, T0] with T0 >= 1")
@@ -253,13 +264,24 @@ class GPT(tnn.Module):
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
             raise ValueError("generate: max_new_tokens must be >= 1")
-        if T0 + max_new_tokens > cfg.block_size:
-            raise ValueError(f"generate: T0 + max_new_tokens = {T0 + max_new_tokens} exceeds block_size "
+        lens = None
+        if prompt_lens is not None:
+            lens = [int(n) for n in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
+            if len(lens) != B:
+                raise ValueError(f"generate: prompt_lens holds {len(lens)} lengths for {B} rows")
+            if min(lens) < 1 or max(lens) > T0:
+                raise ValueError(f"generate: every prompt length must be in 1 .. {T0} (got {lens})")
+        Tlong = T0 if lens is None else max(lens)
+        if Tlong + max_new_tokens > cfg.block_size:
+            raise ValueError(f"generate: T0 + max_new_tokens = {Tlong + max_new_tokens} exceeds block_size "
                              f"{cfg.block_size} (positions are learned and absolute: no sliding window)")
+        if not 0 <= int(pad_token_id) < cfg.vocab_size:
+            raise ValueError("generate: pad_token_id must be a token of the vocabulary")
         if temperature < 0:
             raise ValueError("generate: temperature must be >= 0")
         if top_k is not None and top_k < 1:
             raise ValueError("generate: top_k must be >= 1")
+        D.check_top_p(top_p, "generate")
         if eos_token_id is not None and not 0 <= eos_token_id < cfg.vocab_size:
             raise ValueError("generate: eos_token_id must be a token of the vocabulary")
         dev = self.transformer.wte.weight.device
@@ -275,18 +297,22 @@ class GPT(tnn.Module):
             with torch.no_grad():
                 run = self._generate_gpu if dev.type == "cuda" else self._generate_cpu
                 return run(idx.to(dev).long(), max_new_tokens, float(temperature), top_k, generator, eos_token_id,
-                           use_graph, return_logits, _after_prefill)
+                           use_graph, return_logits, _after_prefill, top_p, lens, int(pad_token_id))
         finally:
             self.train(was_training)
 
-    def _generate_cpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill):
+    def _generate_cpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill,
+                      top_p=None, lens=None, pad=0):
         V = self.config.vocab_size
+        if lens is not None:
+            return self._generate_cpu_ragged(idx, n_new, temperature, top_k, generator, eos, return_logits, top_p,
+                                             lens, pad)
         seq = idx
         fin = torch.zeros(idx.shape[0], dtype=torch.bool)
         kept = []
         for _ in range(n_new):
             logits = self(seq)[:, -1]
-            tok = D.sample_reference(logits, V, generator.next(), temperature, top_k)
+            tok = D.sample_reference(logits, V, generator.next(), temperature, top_k, top_p=top_p)
             if eos is not None:
                 tok = torch.where(fin, torch.full_like(tok, eos), tok)
                 fin = fin | (tok == eos)
@@ -295,8 +321,38 @@ class GPT(tnn.Module):
                 kept.append(logits)
         return (seq, torch.stack(kept, dim=1)) if return_logits else seq
 
-    def _generate_gpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill):
-        ses = DecodeSession(self, idx, n_new, temperature, top_k, generator.state, eos, return_logits)
+    def _generate_cpu_ragged(self, idx, n_new, temperature, top_k, generator, eos, return_logits, top_p, lens, pad):
+        """One right-padded forward per token; row ``b``'s logits are row ``len_b + s - 1`` of it (causal:
+        independent of what follows), gathered into ``[B, V]`` for one sampler call per step, so the
+        Philox row index is ``b`` as on the GPU."""
+        V = self.config.vocab_size
+        B, T0 = idx.shape
+        Tl = max(lens)
+        ln = torch.tensor(lens, dtype=torch.int64)
+        rows = torch.arange(B)
+        real = torch.arange(T0)[None, :] < ln[:, None]
+        out = torch.full((B, T0 + n_new), pad, dtype=torch.int64)
+        out[:, :T0] = torch.where(real, idx, out[:, :T0])
+        seq = torch.zeros(B, Tl + n_new, dtype=torch.int64)        # what the model sees: pad columns hold token 0
+        seq[:, :Tl] = torch.where(real[:, :Tl], idx[:, :Tl], seq[:, :Tl])
+        fin = torch.zeros(B, dtype=torch.bool)
+        kept = []
+        for s in range(n_new):
+            logits = self(seq[:, :Tl + s])[rows, ln + s - 1]
+            tok = D.sample_reference(logits, V, generator.next(), temperature, top_k, top_p=top_p)
+            if eos is not None:
+                tok = torch.where(fin, torch.full_like(tok, eos), tok)
+                fin = fin | (tok == eos)
+            seq[rows, ln + s] = tok
+            out[rows, ln + s] = tok
+            if return_logits:
+                kept.append(logits)
+        return (out, torch.stack(kept, dim=1)) if return_logits else out
+
+    def _generate_gpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill,
+                      top_p=None, lens=None, pad=0):
+        ses = DecodeSession(self, idx, n_new, temperature, top_k, generator.state, eos, return_logits, top_p=top_p,
+                            prompt_lens=lens, pad_token_id=pad)
         if _after_prefill is not None:
             _after_prefill(ses.cache)
         if n_new > 1 and use_graph:
@@ -332,16 +388,28 @@ class DecodeSession:
     """One GPU generation of ``GPT.generate``: the KV cache, the device state and the static buffers.
 
     The constructor runs the prefill -- the prompt, padded to a multiple of 128, through the training
-    kernels, filling the cache -- and samples the first token.  ``step()`` then generates one token per
-    call and touches nothing on the host that changes between tokens, so ``capture()`` can record it once
-    and every ``replay()`` of the returned graph yields the next token.  Call under ``torch.no_grad()``
-    with the model in eval mode (``GPT.generate`` does)."""
+    kernels, filling the cache -- and samples the first token.  With ``prompt_lens`` the window is that of
+    the longest prompt, and the device state carries every row's offset from it.  ``step()`` then generates
+    one token per call and touches nothing on the host that changes between tokens, so ``capture()`` can
+    record it once and every ``replay()`` of the returned graph yields the next token.  Call under
+    ``torch.no_grad()`` with the model in eval mode (``GPT.generate`` does)."""
 
     def __init__(self, model, idx, n_new, temperature=1.0, top_k=None, rng_state=None, eos=None,
-                 return_logits=False):
+                 return_logits=False, top_p=None, prompt_lens=None, pad_token_id=0):
         cfg, t = model.config, model.transformer
         dev = idx.device
-        B, T0 = idx.shape
+        B, Tin = idx.shape
+        D.check_top_p(top_p, "generate")
+        if prompt_lens is None:
+            lens = None
+            T0 = Tin
+        else:
+            lens = [int(n) for n in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
+            if len(lens) != B or min(lens) < 1 or max(lens) > Tin:
+                raise ValueError(f"generate: prompt_lens must hold {B} lengths in 1 .. {Tin} (got {lens})")
+            T0 = max(lens)                       # the longest prompt: window, cache length and base position
+        if T0 + n_new > cfg.block_size:
+            raise ValueError(f"generate: T0 + max_new_tokens = {T0 + n_new} exceeds block_size {cfg.block_size}")
         wte, wpe = t.wte.weight, t.wpe.weight
         if B > D.MAX_ROWS:
             raise NotImplementedError(f"generate: at most {D.MAX_ROWS} sequences on the GPU (got {B})")
@@ -352,30 +420,47 @@ class DecodeSession:
             raise NotImplementedError("generate: the prefill needs a window that is a multiple of 128 "
                                       f"(block_size {cfg.block_size} caps it at {Tpad})")
         self.model, self.T0, self.V = model, T0, cfg.vocab_size
-        self.sampling = (float(temperature), top_k, eos)
+        self.sampling = (float(temperature), top_k, eos, top_p)
         # prefill: the training kernels over the padded prompt (causal: the pad never reaches positions < T0)
         self.cache = D.KVCache(cfg, B, T0 + n_new, dev)
         idx_pad = torch.zeros(B, Tpad, device=dev, dtype=torch.int64)
-        idx_pad[:, :T0] = idx
+        if lens is None:
+            idx_pad[:, :T0] = idx
+        else:                                    # columns >= len_b hold token 0, whatever idx holds there
+            ln = torch.tensor(lens, device=dev, dtype=torch.int64)
+            real = torch.arange(Tin, device=dev)[None, :] < ln[:, None]
+            idx_pad[:, :T0] = torch.where(real[:, :T0], idx[:, :T0], idx_pad[:, :T0])
         x, delta = T.embedding(idx_pad, wte, wpe), None
         for l, blk in enumerate(t.h):
             x, delta, qkv = blk.forward_deferred_qkv(x, delta)
+            # ragged: the cache rows len_b .. T0 - 1 of a shorter row come from pad columns here; each is
+            # overwritten by the decode step that first reaches it (the append at p_b) before any read,
+            # since a step at p_b reads rows <= p_b only
             D.cache_fill(qkv, self.cache, l, T0)
-        # only row T0 - 1 goes through ln_f and the LM head: the [B * Tpad, Vp] logits are never formed
-        h = T.add_layer_norm_residual(x[:, T0 - 1].contiguous(), delta[:, T0 - 1].contiguous(),
-                                      t.ln_f.weight, t.ln_f.bias, t.ln_f.eps)[1]
-        self.state = D.DecodeState(dev, rng_state, pos=T0 - 1, step=0)
-        self.out = torch.zeros(B, T0 + n_new, device=dev, dtype=torch.int64)
-        self.out[:, :T0] = idx
+        # only the last prompt row goes through ln_f and the LM head: the [B * Tpad, Vp] logits are never formed
+        if lens is None:
+            xl, dl = x[:, T0 - 1].contiguous(), delta[:, T0 - 1].contiguous()
+        else:                                    # row len_b - 1 of row b: a gather
+            rows = torch.arange(B, device=dev)
+            xl, dl = x[rows, ln - 1].contiguous(), delta[rows, ln - 1].contiguous()
+        h = T.add_layer_norm_residual(xl, dl, t.ln_f.weight, t.ln_f.bias, t.ln_f.eps)[1]
+        self.state = D.DecodeState(dev, rng_state, pos=T0 - 1, step=0,
+                                   row_offsets=None if lens is None else [n - T0 for n in lens])
+        if lens is None:
+            self.out = torch.zeros(B, T0 + n_new, device=dev, dtype=torch.int64)
+            self.out[:, :T0] = idx
+        else:
+            self.out = torch.full((B, Tin + n_new), int(pad_token_id), device=dev, dtype=torch.int64)
+            self.out[:, :Tin] = torch.where(real, idx, self.out[:, :Tin])
         self.next = torch.zeros(B, device=dev, dtype=torch.int64)
         self.logits_out = (torch.empty(B, n_new, self.V, device=dev, dtype=torch.bfloat16)
                            if return_logits else None)
         self._sample(D.skinny_linear(h, wte))      # token T0; the state now points at it
 
     def _sample(self, logits):
-        temperature, top_k, eos = self.sampling
+        temperature, top_k, eos, top_p = self.sampling
         D.sample(logits, self.V, self.state, temperature, top_k, eos, next=self.next, out=self.out,
-                 logits_out=self.logits_out, T0=self.T0)
+                 logits_out=self.logits_out, T0=self.T0, top_p=top_p)
 
     def step(self):
         """embedding -> blocks (residual adds deferred into the next LayerNorm) -> ln_f -> LM head -> sampler"""

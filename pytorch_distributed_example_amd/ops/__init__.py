@@ -13,8 +13,8 @@ from . import transformer  # noqa: F401
 from . import rng  # noqa: F401
 from .rng import DeviceRNG, dropout_mask, effective_p  # noqa: F401
 from . import decode  # noqa: F401
-from .decode import (DecodeState, KVCache, decode_attention, sample, sample_reference,  # noqa: F401
-                     skinny_linear)
+from .decode import (DecodeState, KVCache, check_top_p, decode_attention, decode_embed,  # noqa: F401
+                     key16_to_float, sample, sample_reference, skinny_linear)
 
 
 def linear(x, weight, bias=None):

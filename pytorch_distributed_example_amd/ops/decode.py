@@ -5,7 +5,9 @@ its CPU twin.
 Everything that changes from token to token -- position, output slot, RNG draw number, the rows'
 "finished" flags -- lives in a small device buffer (``DecodeState``, layout in
 ``csrc/include/pde_decode.h``) that the kernels read and the sampler advances, so one decode step can be
-captured once and replayed per token with no host work in between.
+captured once and replayed per token with no host work in between.  The same buffer holds one constant
+position offset per row, ``off_b = len_b - max(len) <= 0``, for a batch of prompts of different lengths:
+row ``b`` is at position ``pos + off_b`` and its token goes to ``out[b, T0 + off_b + step]``.
 
 Sampling definition (``sample`` on the GPU and ``sample_reference`` in numpy compute the same thing):
 
@@ -16,6 +18,17 @@ Sampling definition (``sample`` on the GPU and ``sample_reference`` in numpy com
   Gumbel noise ``g_v = -log(-log(u_v))``, ``u_v = ((w_v >> 9) + 0.5) * 2^-23`` and ``w_v`` word ``v & 3`` of
   Philox group ``b * ceil(Vp / 4) + (v >> 2)`` at site 0 of the snapshot (``ops/rng.py`` addressing).
   This is the Gumbel-max form of sampling from ``softmax(logits / temperature)``; one draw number per token.
+* ``top_p = P`` in ``(0, 1)`` (``None`` and ``1.0``: off; ignored when ``temperature == 0``) comes after
+  top-k.  With ``C`` the candidates after top-k (all ``V`` columns without it),
+  ``z_v = float(logit_v) * fp32(1 / temperature)``, ``w_v = exp(z_v - max_C z)``, ``W = sum_C w_v`` and, for a
+  bf16 value ``t``, ``M>=(t)`` the sum of ``w_v`` over the candidates with ``logit_v >= t`` (``M>(t)``: with
+  ``>``), the nucleus threshold ``t_p`` is the largest logit value occurring in ``C`` with
+  ``M>=(t_p) >= P * W``, and the kept set is ``{v in C : logit_v >= t_p}``: a threshold value with ties kept,
+  like top-k, never empty, and ``t_p >=`` the top-k threshold, so ``t_p`` is the effective threshold.  The
+  token is the same Gumbel-max over the kept set, same Philox addressing.  The kernel sums ``w_v`` as
+  ``round(2^40 * expf(.))`` in 64-bit integers (order-independent; at most ``50304 * 2^-41`` of ``W`` off),
+  the reference in fp64; ``p_slack`` of ``sample_reference`` says how far ``P * W`` is from the nearest
+  boundary at which the two could disagree.
 
 GPU tensors always run the framework kernels; an unsupported shape raises ``NotImplementedError``.
 """
@@ -32,24 +45,41 @@ from . import rng as R
 
 _BF16 = torch.bfloat16
 
-STATE_WORDS = 24          # pde_decode.h
-_RNG, _POS, _STEP, _FIN = 0, 4, 5, 8
+STATE_WORDS = 40          # pde_decode.h
+_RNG, _POS, _STEP, _FIN, _OFF = 0, 4, 5, 8, 24
 MAX_ROWS = 16
 
 
-class DecodeState:
-    """The device-side state of a generation: RNG words, position, step, finished flags (int32 x 24)."""
+def check_top_p(top_p, who: str = "sample"):
+    """``None`` or a value in ``(0, 1]``; returns whether the nucleus stage is on (``None`` and 1.0: off)."""
+    if top_p is None:
+        return False
+    if not 0.0 < float(top_p) <= 1.0:
+        raise ValueError(f"{who}: top_p must be None or in (0, 1] (got {top_p})")
+    return float(top_p) < 1.0
 
-    def __init__(self, device=None, rng_state=None, pos: int = 0, step: int = 0):
+
+class DecodeState:
+    """The device-side state of a generation: RNG words, position, step, finished flags and per-row
+    position offsets (int32 x 40)."""
+
+    def __init__(self, device=None, rng_state=None, pos: int = 0, step: int = 0, row_offsets=None):
         self.device = torch.device("cpu" if device is None else device)
         self.buf = torch.zeros(STATE_WORDS, dtype=torch.int32, device=self.device)
-        self.reset(rng_state, pos, step)
+        self.reset(rng_state, pos, step, row_offsets)
 
-    def reset(self, rng_state=None, pos: int = 0, step: int = 0):
-        """Position / step from the host, RNG words copied from a ``DeviceRNG`` state or snapshot (a
-        device-to-device copy: no host read); the finished flags are cleared."""
+    def reset(self, rng_state=None, pos: int = 0, step: int = 0, row_offsets=None):
+        """Position / step / row offsets from the host, RNG words copied from a ``DeviceRNG`` state or
+        snapshot (a device-to-device copy: no host read); the finished flags are cleared.  ``row_offsets``
+        (up to 16 ints ``<= 0``, default all 0) are ``len_b - max(len)`` of a ragged prompt batch: row ``b``
+        is at position ``pos + row_offsets[b]``."""
         init = torch.zeros(STATE_WORDS, dtype=torch.int32)
         init[_POS], init[_STEP] = int(pos), int(step)
+        if row_offsets is not None:
+            offs = [int(o) for o in (row_offsets.tolist() if torch.is_tensor(row_offsets) else row_offsets)]
+            if len(offs) > MAX_ROWS or any(o > 0 for o in offs):
+                raise ValueError(f"row_offsets: at most {MAX_ROWS} values <= 0 (got {offs})")
+            init[_OFF:_OFF + len(offs)] = torch.tensor(offs, dtype=torch.int32)
         self.buf.copy_(init)
         if rng_state is not None:
             if tuple(rng_state.shape) != (4,) or rng_state.dtype != torch.int32:
@@ -65,8 +95,18 @@ class DecodeState:
     def finished(self):
         return self.buf[_FIN:_FIN + MAX_ROWS]
 
+    @property
+    def row_offsets(self):
+        return self.buf[_OFF:_OFF + MAX_ROWS]
+
     def pos(self) -> int:
+        """The base position: that of the rows with offset 0 (the longest prompts)."""
         return int(self.buf[_POS].item())
+
+    def row_pos(self, B: int = MAX_ROWS):
+        """The positions of rows ``0 .. B-1`` as a list: base position plus row offset (a host read)."""
+        w = self.buf.cpu()
+        return [int(w[_POS]) + (int(w[_OFF + b]) if b < MAX_ROWS else 0) for b in range(B)]
 
     def step(self) -> int:
         return int(self.buf[_STEP].item())
@@ -153,7 +193,9 @@ def decode_attention(qkv_row, cache: KVCache, layer: int, state: DecodeState):
     """One decode step of causal attention: append the new token's K and V (from its c_attn row
     ``[B, 3C]``) at the state's position ``p`` and return ``softmax(q K[0..p]^T / 8) V[0..p]`` as
     ``[B, C]``.  Fixed 128-key chunks with fp32 partials combined in chunk order: the output for a given
-    ``p`` is bit-identical across runs and independent of the cache length."""
+    ``p`` is bit-identical across runs and independent of the cache length.  ``p`` is per row, ``p_b`` = the
+    state's position plus row ``b``'s offset, and a row's output depends on its own ``p_b`` only: it is
+    bit-identical to a call in which every row is at ``p_b``."""
     B, C3 = qkv_row.shape
     H = cache.n_head
     if C3 != 3 * H * 64 or B != cache.batch:
@@ -163,28 +205,34 @@ def decode_attention(qkv_row, cache: KVCache, layer: int, state: DecodeState):
     if qkv_row.is_cuda:
         if qkv_row.dtype != _BF16 or cache.data.dtype != _BF16:
             raise NotImplementedError("decode_attention: the GPU path is bf16")
+        if B > MAX_ROWS:
+            raise NotImplementedError(f"decode_attention: at most {MAX_ROWS} rows on the GPU (got {B})")
         out = torch.empty(B, C, device=qkv_row.device, dtype=_BF16)
         kernels().decode_attention(qkv_row if qkv_row.is_contiguous() else qkv_row.contiguous(), cache.layer(layer),
                                    state.buf, cache.partials(), out, H, scale)
         return out
-    p = state.pos()
     q, k, v = (t.reshape(B, H, 64) for t in qkv_row.split(C, dim=1))
-    cache.data[layer, 0, :, :, p] = k
-    cache.data[layer, 1, :, :, p] = v
-    Kc, Vc = cache.data[layer, 0, :, :, :p + 1].float(), cache.data[layer, 1, :, :, :p + 1].float()
-    s = torch.einsum("bhd,bhtd->bht", q.float(), Kc) * scale
-    return torch.einsum("bht,bhtd->bhd", torch.softmax(s, -1), Vc).reshape(B, C).to(qkv_row.dtype)
+    rows = []
+    for b, p in enumerate(state.row_pos(B)):
+        cache.data[layer, 0, b, :, p] = k[b]
+        cache.data[layer, 1, b, :, p] = v[b]
+        Kc, Vc = cache.data[layer, 0, b, :, :p + 1].float(), cache.data[layer, 1, b, :, :p + 1].float()
+        s = torch.einsum("hd,htd->ht", q[b].float(), Kc) * scale
+        rows.append(torch.einsum("ht,htd->hd", torch.softmax(s, -1), Vc).reshape(C))
+    return torch.stack(rows).to(qkv_row.dtype)
 
 
 def decode_embed(tok, wte, wpe, state: DecodeState):
-    """``x[b] = wte[tok[b]] + wpe[p]`` with ``p`` read from the state."""
+    """``x[b] = wte[tok[b]] + wpe[p_b]`` with ``p_b`` (position plus row offset) read from the state."""
     if wte.is_cuda:
         if wte.dtype != _BF16 or wpe.dtype != _BF16 or wte.shape[1] % 8:
             raise NotImplementedError("decode_embed: the GPU path is bf16 with C % 8 == 0")
+        if tok.numel() > MAX_ROWS:
+            raise NotImplementedError(f"decode_embed: at most {MAX_ROWS} rows on the GPU (got {tok.numel()})")
         out = torch.empty(tok.numel(), wte.shape[1], device=wte.device, dtype=_BF16)
         kernels().decode_embed(tok, wte, wpe, state.buf, out)
         return out
-    return F.embedding(tok, wte) + wpe[state.pos()].unsqueeze(0)
+    return F.embedding(tok, wte) + wpe[torch.tensor(state.row_pos(tok.numel()), dtype=torch.int64)]
 
 
 # --------------------------------------------------------------------------------------- sampling
@@ -192,29 +240,78 @@ def _snapshot_of(snapshot_or_state):
     return snapshot_or_state.rng if isinstance(snapshot_or_state, DecodeState) else snapshot_or_state
 
 
+def _nucleus(lg, cand, inv_temp, ps):
+    """The nucleus thresholds of the rows of ``lg`` (fp64 ``[B, V]``) over the candidates ``cand`` for each
+    mass ``P`` in ``ps``: a list of ``(t_p, M>(t_p) / W, M>=(t_p) / W)``, each ``[B]``.  ``W`` is the last value
+    of the same running sum the masses are read from, so ``P = 1`` always finds the smallest candidate."""
+    B, V = lg.shape
+    z = np.where(cand, lg * inv_temp, -np.inf)
+    w = np.exp(z - z.max(axis=1, keepdims=True))              # 0 outside the candidates
+    order = np.argsort(-lg, axis=1, kind="stable")
+    sv = np.take_along_axis(lg, order, axis=1)
+    sc = np.take_along_axis(cand, order, axis=1)
+    cw = np.cumsum(np.take_along_axis(w, order, axis=1), axis=1)
+    W = cw[:, -1]
+    end = np.ones((B, V), dtype=bool)                         # last column of a run of equal values
+    end[:, :-1] = sv[:, :-1] != sv[:, 1:]
+    rows = np.arange(B)
+    res = []
+    for P in ps:
+        ok = end & sc & (cw >= (P * W)[:, None])
+        i = ok.argmax(axis=1)                                 # first in descending order = largest value
+        assert ok[rows, i].all()
+        t = sv[rows, i]
+        above = np.where(sv > t[:, None], cw, 0.0).max(axis=1)    # cw is non-decreasing: M>(t)
+        res.append((t, above / W, cw[rows, i] / W))
+    return res
+
+
 def sample_reference(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=None,
-                     return_info: bool = False):
+                     return_info: bool = False, top_p=None, eps: float = 1e-4, _threshold=None):
     """The sampling definition in numpy, fp64, from the same Philox words as the kernel.  ``logits`` is
     ``[B, Vp]`` (any float dtype; columns ``>= V`` never participate).  Returns the ``[B]`` int64 tokens,
-    and with ``return_info`` also a dict: ``threshold`` (the k-th largest value per row, ``-inf`` without
-    top-k), ``ncand`` (candidates per row) and ``gap`` (best minus runner-up score per row, ``inf`` with a
-    single candidate or for greedy)."""
+    and with ``return_info`` also a dict: ``threshold`` (the effective threshold per row: the k-th largest
+    value, raised to the nucleus threshold with ``top_p``; ``-inf`` with neither), ``ncand`` (candidates per
+    row) and ``gap`` (best minus runner-up score per row, ``inf`` with a single candidate or for greedy).
+
+    With ``top_p`` on, the dict also holds ``threshold_p`` (``t_p`` of the module docstring), ``p_slack``
+    (``min(top_p * W - M>(t_p), M>=(t_p) - top_p * W) / W``: how far the target mass is from the nearest
+    boundary between two thresholds) and ``threshold_p_bracket``, the pair ``(t_p at top_p + eps, t_p at
+    top_p - eps)`` with ``top_p +- eps`` clamped into ``(0, 1]``: the thresholds an implementation whose
+    mass sums are off by less than ``eps * W`` can arrive at lie between the two.
+
+    ``_threshold`` (``[B]`` values) replaces the computed effective threshold: the token for a threshold
+    chosen elsewhere."""
     if logits.dim() != 2 or not 1 <= V <= logits.shape[1]:
         raise ValueError("sample_reference: logits [B, Vp] with 1 <= V <= Vp")
     if temperature < 0:
         raise ValueError("temperature must be >= 0")
     if top_k is not None and top_k < 1:
         raise ValueError("top_k must be >= 1")
+    nucleus = check_top_p(top_p, "sample_reference")
     B, Vp = logits.shape
     lg = logits.detach().float().cpu().numpy().astype(np.float64)[:, :V]
     thr = np.full(B, -np.inf)
     gap = np.full(B, np.inf)
+    extra = {}
     if temperature == 0:
         tok = lg.argmax(axis=1)                       # first occurrence = lowest index
         ncand = np.full(B, V)
     else:
-        if top_k is not None and top_k < V:
-            thr = np.partition(lg, V - top_k, axis=1)[:, V - top_k]
+        inv_temp = float(np.float32(1.0 / temperature))
+        if _threshold is not None:
+            thr = np.asarray(_threshold, dtype=np.float64).reshape(B)
+        else:
+            if top_k is not None and top_k < V:
+                thr = np.partition(lg, V - top_k, axis=1)[:, V - top_k]
+            if nucleus:
+                P = float(top_p)
+                tiny = float(np.finfo(np.float64).tiny)
+                at, hi, lo = _nucleus(lg, lg >= thr[:, None], inv_temp,
+                                      [P, min(P + eps, 1.0), max(P - eps, tiny)])
+                thr = at[0]
+                extra = {"threshold_p": at[0], "p_slack": np.minimum(P - at[1], at[2] - P),
+                         "threshold_p_bracket": (hi[0], lo[0])}
         cand = lg >= thr[:, None]
         ngrp = (Vp + 3) // 4
         groups = (np.arange(B, dtype=np.uint64)[:, None] * np.uint64(ngrp)
@@ -222,7 +319,6 @@ def sample_reference(logits, V: int, snapshot_or_state, temperature: float = 1.0
         w = np.stack(R._words(_snapshot_of(snapshot_or_state), 0, groups), axis=2).reshape(B, ngrp * 4)[:, :V]
         u = ((w >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
         g = -np.log(-np.log(u))
-        inv_temp = float(np.float32(1.0 / temperature))
         score = np.where(cand, lg * inv_temp + g, -np.inf)
         tok = score.argmax(axis=1)
         ncand = cand.sum(axis=1)
@@ -232,7 +328,7 @@ def sample_reference(logits, V: int, snapshot_or_state, temperature: float = 1.0
                 gap = np.where(ncand > 1, top2[:, 1] - top2[:, 0], np.inf)
     tok = torch.from_numpy(tok.astype(np.int64))
     if return_info:
-        return tok, {"threshold": thr, "ncand": ncand, "gap": gap}
+        return tok, {"threshold": thr, "ncand": ncand, "gap": gap, **extra}
     return tok
 
 
@@ -246,19 +342,23 @@ def key16_to_float(key):
 
 
 def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=None, eos_token_id=None,
-           next=None, out=None, logits_out=None, T0: int = 0, threshold_out=None):
+           next=None, out=None, logits_out=None, T0: int = 0, threshold_out=None, top_p=None):
     """Sample one token per row of the ``[B, Vp]`` bf16 logits on the device (one block per row).
 
     With a ``DecodeState`` the launch also does the bookkeeping of a generation step: the token goes to
-    ``next[b]`` and ``out[b, T0 + step]``; a finished row emits ``eos_token_id`` and a row that emits it
+    ``next[b]`` and ``out[b, T0 + off_b + step]`` (``off_b``: the state's row offset, 0 for a batch of one
+    prompt length); a finished row emits ``eos_token_id`` and a row that emits it
     becomes finished; ``logits_out[b, step, :]`` receives the row's first ``V`` logits; then position, step
-    and draw number advance.  ``threshold_out`` (int32 ``[B]``, GPU, for tests) receives the top-k threshold
-    as the kernel's order-preserving 16-bit key (``key16_to_float`` decodes it).  With a plain 4-word RNG snapshot a temporary state is used.  Returns ``next``.
+    and draw number advance.  ``threshold_out`` (int32 ``[B]``, GPU, for tests) receives the effective
+    threshold (top-k, raised by ``top_p``) as the kernel's order-preserving 16-bit key (``key16_to_float``
+    decodes it).  ``top_p`` of ``None`` or 1.0 runs the sampler without the nucleus stage.  With a plain
+    4-word RNG snapshot a temporary state is used.  Returns ``next``.
     CPU tensors run ``sample_reference`` (with the same bookkeeping on a ``DecodeState``)."""
     if temperature < 0:
         raise ValueError("temperature must be >= 0")
     if top_k is not None and top_k < 1:
         raise ValueError("top_k must be >= 1")
+    nucleus = check_top_p(top_p, "sample")
     B = logits.shape[0]
     if isinstance(snapshot_or_state, DecodeState):
         state = snapshot_or_state
@@ -270,15 +370,16 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
         out = torch.zeros(B, T0 + 1, device=logits.device, dtype=torch.int64)
     eos = -1 if eos_token_id is None else int(eos_token_id)
     if not logits.is_cuda:
-        tok = sample_reference(logits, V, state, temperature, top_k)
+        tok = sample_reference(logits, V, state, temperature, top_k, top_p=top_p)
         step = state.step()
         if eos >= 0:
             fin = state.finished[:B].bool()
             tok = torch.where(fin, torch.full_like(tok, eos), tok)
             state.finished[:B] = (fin | (tok == eos)).int()
         next.copy_(tok)
-        if T0 + step < out.shape[1]:
-            out[:, T0 + step] = tok
+        for b, off in enumerate(state.row_offsets[:B].tolist() + [0] * max(B - MAX_ROWS, 0)):
+            if 0 <= T0 + off + step < out.shape[1]:
+                out[b, T0 + off + step] = tok[b]
         if logits_out is not None and step < logits_out.shape[1]:
             logits_out[:, step] = logits[:, :V].to(logits_out.dtype)
         state.advance_()
@@ -290,5 +391,6 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
     greedy = temperature == 0
     inv_temp = 0.0 if greedy else float(np.float32(1.0 / temperature))
     kernels().decode_sample(logits, int(V), state.buf, next, out, logits_out, int(T0), inv_temp, greedy,
-                            0 if top_k is None else int(top_k), eos, threshold_out)
+                            0 if top_k is None else int(top_k), eos, threshold_out,
+                            float(top_p) if nucleus else 0.0)
     return next

@@ -14,7 +14,15 @@ Achieved bytes/s of the decode step = (every parameter once in bf16, ``wte`` onl
 plus the K and V rows read, mean over the window) / median ms per token; compared with the 6.29 TB/s
 achievable HBM bandwidth of MI355X_MICROARCH.md.  One JSON line per batch size.
 
+Sampling is temperature 1.0 with ``--top-k`` (default 50, 0: none) and ``--top-p`` (default: off).  With
+``--ragged`` the prompts of a batch have lengths spread evenly from 1 to ``--context`` (a batch of one keeps
+``--context``), so the rows sit at different positions; the K / V bytes are then those of the rows' own
+contexts.  ``--sampler-reps N`` also times the sampler launch alone (``k_sample`` and its one-thread tail) on
+the logits of the prefill: N back-to-back calls between one event pair, with the run's settings and with
+top-p off.
+
     python tools/gpt2_decode_bench.py [--context 512] [--window 64] [--rounds 5] [--batch-sizes 1 16]
+                                      [--top-k 50] [--top-p P] [--ragged] [--sampler-reps N]
 """
 import argparse
 import json
@@ -30,6 +38,7 @@ import torch  # noqa: E402
 from pytorch_distributed_example_amd.models import GPTConfig, build_gpt2  # noqa: E402
 from pytorch_distributed_example_amd.models.gpt2 import DecodeSession  # noqa: E402
 from pytorch_distributed_example_amd.ops import DeviceRNG  # noqa: E402
+from pytorch_distributed_example_amd.ops import decode as D  # noqa: E402
 
 HBM_BYTES_PER_S = 6.29e12
 
@@ -38,8 +47,32 @@ def events(n):
     return [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
 
 
-def bench_decode(model, idx, a):
-    ses = DecodeSession(model, idx, a.window + 1, 1.0, 50, DeviceRNG(0, device=idx.device).state)
+def prompt_lens(B, context):
+    """Lengths spread evenly from 1 to ``context``"""
+    return [context] if B == 1 else [1 + round(b * (context - 1) / (B - 1)) for b in range(B)]
+
+
+def bench_sampler(B, cfg, top_k, top_p, reps, dev):
+    """us per sampler launch (k_sample + tail), ``reps`` calls between one event pair"""
+    logits = (torch.randn(B, cfg.padded_vocab, device=dev) * 3).to(torch.bfloat16)
+    state = D.DecodeState(dev, DeviceRNG(0, device=dev).state)
+    nxt = torch.zeros(B, device=dev, dtype=torch.int64)
+    out = torch.zeros(B, 1, device=dev, dtype=torch.int64)
+    for _ in range(10):
+        D.sample(logits, cfg.vocab_size, state, 1.0, top_k, next=nxt, out=out, top_p=top_p)
+    e0, e1 = events(1)[0]
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(reps):
+        D.sample(logits, cfg.vocab_size, state, 1.0, top_k, next=nxt, out=out, top_p=top_p)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps
+
+
+def bench_decode(model, idx, a, lens=None):
+    ses = DecodeSession(model, idx, a.window + 1, 1.0, a.top_k or None, DeviceRNG(0, device=idx.device).state,
+                        top_p=a.top_p, prompt_lens=lens)
     graph = ses.capture()
     start = (ses.state.buf.clone(), ses.next.clone())
 
@@ -91,8 +124,12 @@ def main():
     ap.add_argument("--context", type=int, default=512)
     ap.add_argument("--window", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--recompute-reps", type=int, default=20)
+    ap.add_argument("--recompute-reps", type=int, default=20, help="0: skip the recompute baseline")
     ap.add_argument("--batch-sizes", type=int, nargs="+", default=[1, 16])
+    ap.add_argument("--top-k", type=int, default=50, help="0: no top-k")
+    ap.add_argument("--top-p", type=float, default=None, help="nucleus mass in (0, 1]; default: off")
+    ap.add_argument("--ragged", action="store_true", help="prompt lengths spread from 1 to --context")
+    ap.add_argument("--sampler-reps", type=int, default=0, help="also time the sampler launch alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("gpt2_decode_bench: needs a GPU (no CPU fallback: a CPU time says nothing about the kernels)")
@@ -104,10 +141,17 @@ def main():
         for B in a.batch_sizes:
             idx = torch.randint(0, cfg.vocab_size, (B, a.context), device=dev,
                                 generator=torch.Generator(dev).manual_seed(B))
-            per_replay, per_window, eager = bench_decode(model, idx, a)
-            rec = bench_recompute(model, idx, a.recompute_reps)
-            mean_keys = a.context + (a.window + 1) / 2.0          # keys read at positions context .. context+window-1
-            kv_bytes = cfg.n_layer * 2 * B * cfg.n_head * mean_keys * 64 * 2
+            lens = prompt_lens(B, a.context) if a.ragged else None
+            per_replay, per_window, eager = bench_decode(model, idx, a, lens)
+            rec = bench_recompute(model, idx, a.recompute_reps) if a.recompute_reps > 0 else None
+            # keys read at positions len .. len + window - 1, summed over the rows
+            mean_keys = sum(n + (a.window + 1) / 2.0 for n in (lens or [a.context] * B))
+            kv_bytes = cfg.n_layer * 2 * cfg.n_head * mean_keys * 64 * 2
+            extra = {"top_k": a.top_k, "top_p": a.top_p, "prompt_lens": lens}
+            if a.sampler_reps > 0:
+                extra["sampler_us_per_launch"] = {
+                    "this_run": round(bench_sampler(B, cfg, a.top_k or None, a.top_p, a.sampler_reps, dev), 2),
+                    "top_p_off": round(bench_sampler(B, cfg, a.top_k or None, None, a.sampler_reps, dev), 2)}
             ms = statistics.median(per_replay)
             bps = (weight_bytes + kv_bytes) / (ms * 1e-3)
             print(json.dumps({
@@ -117,13 +161,13 @@ def main():
                                               "max": round(max(per_replay), 4),
                                               "window_mean_median": round(statistics.median(per_window), 4)},
                 "decode_eager_ms_per_token_median": round(statistics.median(eager), 4),
-                "recompute_forward_ms_per_token": {"median": round(statistics.median(rec), 4),
-                                                   "min": round(min(rec), 4), "max": round(max(rec), 4)},
-                "speedup_vs_recompute": round(statistics.median(rec) / ms, 2),
+                "recompute_forward_ms_per_token": rec and {"median": round(statistics.median(rec), 4),
+                                                           "min": round(min(rec), 4), "max": round(max(rec), 4)},
+                "speedup_vs_recompute": rec and round(statistics.median(rec) / ms, 2),
                 "tokens_per_s_decode": round(B / (ms * 1e-3), 1),
                 "bytes_per_token": {"weights": weight_bytes, "kv": int(kv_bytes)},
                 "achieved_bytes_per_s": round(bps, 1),
-                "share_of_6.29TBps": round(bps / HBM_BYTES_PER_S, 4)}), flush=True)
+                "share_of_6.29TBps": round(bps / HBM_BYTES_PER_S, 4), **extra}), flush=True)
 
 
 if __name__ == "__main__":
