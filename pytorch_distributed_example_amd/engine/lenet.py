@@ -19,17 +19,22 @@ xGMI peer kernel -- by timing whole steps on the node: ``autotune_schedule``)
 * The dataset is device resident; the epoch permutation is uploaded once per epoch and batch b of
   the epoch is gathered inside F1 from a device batch counter that F2 advances, so a
   captured hipGraph replays consecutive steps with no host work at all.
+
+In the code: ``_launch`` issues ``_forward`` (F1-F3), ``_fc_backward`` (B1) and then the method of the
+current schedule mode (``_step_none`` / ``_step_serial`` / ``_step_flat`` / ``_step_overlap`` /
+``_step_overlap2`` / ``_step_fused``, table ``_STEP``), which places ``_conv_backward`` (B2), the
+all-reduces and ``_opt`` on the two streams.  A schedule is a ``Schedule(mode, routes)`` value.
 """
 from __future__ import annotations
 
-import math
 import os
-from typing import Optional
+import time
+from typing import NamedTuple, Optional
 
 import torch
 
 from .._ext import kernels
-from ..ops.lenet_fused import pack_conv2_weight
+from ..ops.lenet_fused import LeNetWorkspace, pack_conv2_weight
 from ..parallel.flat import FlatLayout
 
 FC_BUCKET = ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
@@ -39,6 +44,54 @@ C1_NREP = 16          # conv1 gradient replicas (atomic contention: 128 images -
 C1_STRIDE = 576       # conv1.weight (500 -> 512 slot) + conv1.bias (20 -> 64 slot); v2: int64 [500 | 20] + pad
 C2_NREP = 16          # conv2 wgrad slabs of the v2 step (one per 8-image group, folded inside the launch)
 C2_STRIDE = 25088     # slab: conv2.weight [25000] | pad | conv2.bias [50] at 25024
+
+# communication schedule (W > 1): "overlap" = fc bucket all-reduced on the comm stream beside
+# the conv backward (conv bucket on the comm stream too: four cross-stream edges per step);
+# "overlap2" = the same fc overlap, the conv bucket after it on the comm stream and one join
+# before the whole optimizer (three edges); "flat" = one all-reduce on the comm stream after backward; "serial" = one
+# all-reduce on the compute stream (no cross-stream edges: in a hipGraph each edge between
+# kernels on different streams measured 5-9 us, see autotune_schedule); "fused" = the fc
+# bucket is all-reduced by side blocks of the conv backward kernel (xGMI peer protocol), the
+# conv bucket after it on the compute stream; "none" = the comm path's compute alone (autotune probe)
+MODES = ("overlap", "overlap2", "flat", "serial", "fused", "none")
+
+
+class Schedule(NamedTuple):
+    """One communication schedule: a mode of ``MODES`` and the route of each all-reduced buffer,
+    keyed by the buffer's numel ("rccl", the peer kernel "peer1" / "peer2", "pfold" / "pfold2" for
+    the whole buffer under "serial", "adam1" / "adam2" for the conv bucket under "fused")."""
+    mode: str
+    routes: dict
+
+    @classmethod
+    def parse(cls, label: str) -> "Schedule":
+        """From an autotuner label, e.g. ``"serial 431296:peer1"`` or
+        ``"overlap2 25664:peer1,405632:rccl"`` (mode, then bucket numel:route pairs)."""
+        mode, _, rest = label.strip().partition(" ")
+        if mode not in MODES:
+            raise ValueError(f"unknown schedule mode {mode!r}")
+        routes = {}
+        for kv in filter(None, rest.split(",")):
+            n, sep, route = kv.partition(":")
+            if not (n.strip().isdigit() and sep and route.strip()):
+                raise ValueError(f"malformed numel:route pair {kv!r} in schedule {label!r}")
+            routes[int(n)] = route.strip()
+        return cls(mode, routes)
+
+    def label(self) -> str:
+        return (self.mode + " " + ",".join(f"{n}:{r}" for n, r in sorted(self.routes.items()))).rstrip()
+
+    def route(self, buf: torch.Tensor, default: Optional[str] = None) -> Optional[str]:
+        return self.routes.get(buf.numel(), default)
+
+    @property
+    def uses_peer(self) -> bool:
+        return self.mode == "fused" or any(r != "rccl" for r in self.routes.values())
+
+    @property
+    def cross_stream(self) -> bool:
+        """Kernels on both streams: every cross-stream edge costs join latency in a replayed hipGraph."""
+        return self.mode in ("overlap", "overlap2", "flat")
 
 
 class LeNetTrainStep:
@@ -57,23 +110,15 @@ class LeNetTrainStep:
         self.momentum = float(momentum)
         self.comm = comm
         self.world = comm.world_size if comm is not None else 1
-        # communication schedule (W > 1): "overlap" = fc bucket all-reduced on the comm stream beside
-        # the conv backward (conv bucket on the comm stream too: four cross-stream edges per step);
-        # "overlap2" = the same fc overlap, the conv bucket after it on the comm stream and one join
-        # before the whole optimizer (three edges); "flat" = one all-reduce on the comm stream after backward; "serial" = one
-        # all-reduce on the compute stream (no cross-stream edges: in a hipGraph each edge between
-        # kernels on different streams measured 5-9 us, see autotune_schedule); "fused" = the fc
-        # bucket is all-reduced by side blocks of the conv backward kernel (xGMI peer protocol), the
-        # conv bucket after it on the compute stream
-        self.mode = "overlap" if overlap else "flat"
+        self.mode = "overlap" if overlap else "flat"      # one of MODES
         self._peer_dev = None
         self._ipdev = None            # PeerIpDev bytes of the registered flat gradients ("pfold" route)
         self._fold_sync = None
-        self.ar_epoch = torch.full((1,), -1, device=p0.device, dtype=torch.int64)   # fused-Adam all-reduce
+        dev = self.device
+        self.ar_epoch = torch.full((1,), -1, device=dev, dtype=torch.int64)   # fused-Adam all-reduce
         # force_comm: run the comm-stream/event path even at world size 1 (1-GPU testing of the W>1 path)
         self.comm_on = comm is not None and (self.world > 1 or force_comm)
         self.K = kernels()
-        dev = self.device
         # v2 step (csrc/kernels/lenet_v2.hip): prefetched batches, LDS-DMA weight staging, 8-wave conv
         # forward, co-resident conv backward that reduces its weight gradients deterministically inside
         # the launch (conv2: 16 per-image-group slabs folded in group order by the last-arriving block
@@ -100,71 +145,21 @@ class LeNetTrainStep:
         if self.comm_on and mode == "defer":
             mode = "ext"
         self.bwd_mode = mode if self.v2 else "v1"
-        dev = self.device
-        named = [(n, tuple(p.shape)) for n, p in net.named_parameters()]
-        if self.bwd_mode == "defer":
-            # gradient replicas in the flat buffer (replica 0 = the canonical slot), folded in fixed order
-            # by the optimizer's fold blocks: conv1 as 16 atomic-add replicas, conv2 as 16 image-group slabs
-            self.layout = FlatLayout(named, [FC_BUCKET, CONV_BUCKET + ["conv2.grad_replicas"]],
-                                     extra_shapes={"conv1.grad_replicas": ((C1_NREP - 1) * C1_STRIDE,),
-                                                   "conv2.grad_replicas": ((C2_NREP - 1) * C2_STRIDE,)})
-        elif self.v2:
-            self.layout = FlatLayout(named, [FC_BUCKET, CONV_BUCKET_V2])
-        else:
-            self.layout = FlatLayout(named, [FC_BUCKET, CONV_BUCKET],
-                                     extra_shapes={"conv1.grad_replicas": ((C1_NREP - 1) * C1_STRIDE,)})
-        self.params, self.grads = self.layout.bind(net)
-        V = self.layout.view
-        self.p = {n: V(self.params, n) for n in self.layout.param_names}
-        self.g = {n: V(self.grads, n) for n in self.layout.param_names}
-        self.off = {n: self.layout.slots[n].offset for n in self.layout.param_names}
-        c1 = self.off["conv1.weight"]
-        self.c1_off = c1
-        self.c2_off = self.off["conv2.weight"]
-        self.bucket_grads = [self.layout.bucket_view(self.grads, i) for i in range(2)]
-        o = self.off
-        assert o["conv1.bias"] == c1 + 512 and o["conv2.bias"] == self.c2_off + 25024
-        if self.v2:
-            self.c1rep = torch.zeros(C1_NREP * C1_STRIDE, device=dev, dtype=torch.int64)   # kept zero by the kernel
-            self.tick = torch.zeros(32, device=dev, dtype=torch.int32)                      # arrival counters
-        if self.bwd_mode == "defer":
-            assert self.layout.slots["conv1.grad_replicas"].offset == c1 + C1_STRIDE
-            assert self.layout.slots["conv2.grad_replicas"].offset == self.c2_off + C2_STRIDE
-            self.c1part = self.grads[c1: c1 + C1_NREP * C1_STRIDE]
-            self.slab = self.grads[self.c2_off: self.c2_off + C2_NREP * C2_STRIDE]
-            self.zero_view = self.c1part              # zeroed by the conv forward (atomic targets)
-        elif self.v2:
-            assert o["conv2.weight"] == c1 + C1_STRIDE
-            self.slab = torch.zeros(C2_NREP * C2_STRIDE, device=dev, dtype=torch.float32)
-            self.c1part = torch.zeros(C1_NREP * C1_STRIDE, device=dev, dtype=torch.float32)   # unused in fold mode
-            self.c1img = torch.zeros(self.B * 520, device=dev, dtype=torch.float32)          # ext mode
-            self.zero_view = None
-        else:
-            assert self.layout.slots["conv1.grad_replicas"].offset == c1 + C1_STRIDE
-            self.g_c1w_rep = self.grads[c1: c1 + C1_NREP * C1_STRIDE]
-            self.g_c1b_rep = self.grads[c1 + 512: c1 + C1_NREP * C1_STRIDE]
-            self.zero_view = self.bucket_grads[1]
+        self._bind_layout(net)
         self.m = torch.zeros_like(self.params)
         self.v = torch.zeros_like(self.params) if optimizer == "adam" else self.m
         self.counters = torch.zeros(2, device=dev, dtype=torch.int64)   # [optimizer step, batch in epoch]
         self.arrive = torch.zeros(1, device=dev, dtype=torch.int32)
+        f32 = dict(device=dev, dtype=torch.float32)
+        B = self.B
+        self.ws = LeNetWorkspace(B, dev)      # activations kept between forward and backward, v2 weight image
         if self.v2:
-            self.Wp = torch.zeros(2 * 72 * 256, device=dev, dtype=torch.float32)   # padding stays zero
+            self.Wp = self.ws.Wp
             self.K.lenet_pack_w2_v2(self.p["conv2.weight"].detach().contiguous(), self.Wp)
             self.Wt2 = None
         else:
             self.Wt2 = pack_conv2_weight(self.p["conv2.weight"])
-        self.pack_off = self.layout.slots["conv2.weight"].offset
-        f32 = dict(device=dev, dtype=torch.float32)
-        B = self.B
-        self.P1 = torch.empty(B * 2880, **f32)
-        self.A1 = torch.empty(B * 2880, device=dev, dtype=torch.uint8)
-        self.P2 = torch.empty(B * 800, **f32)
-        self.A2 = torch.empty(B * 800, device=dev, dtype=torch.uint8)
-        self.H1 = torch.empty(B * 500, **f32)
-        self.dZ1 = torch.empty(B * 500, **f32)
-        self.dZ2 = torch.empty(B * 10, **f32)
-        self.dP2m = torch.empty(B * 800, **f32)
+        self.pack_off = self.c2_off
         self.cur_row = torch.zeros(B, device=dev, dtype=torch.int32)
         self.cur_lbl = torch.zeros(B, device=dev, dtype=torch.int64)
         # v2 prefetch buffers, double-buffered by step parity q (host-tracked; baked into captured graphs)
@@ -181,8 +176,6 @@ class LeNetTrainStep:
         self.eval_correct = torch.zeros(1, device=dev, dtype=torch.int64)
         self.comm_stream = torch.cuda.Stream(device=dev) if self.comm_on else None
         self._ev = {k: torch.cuda.Event() for k in ("fc", "conv", "fc_done")}
-        self.bucket_ranges = [tuple(r) for r in self.layout.bucket_ranges]
-        assert self.bucket_ranges[0][0] == 0 and self.bucket_ranges[1][0] >= self.bucket_ranges[0][1]
         if self.comm_on and hasattr(comm, "enable_peer") and not comm.routes:
             # small buckets: time the xGMI peer all-reduce against RCCL at exactly these sizes, on the
             # flat gradient buffer itself, registered so the peer routes read it in place
@@ -199,6 +192,54 @@ class LeNetTrainStep:
         self._lr_host = None
         if lr_schedule is not None:
             self.set_lr_table(lr_schedule)
+
+    def _bind_layout(self, net):
+        """Lay parameters and gradients out flat in bucket order for ``self.bwd_mode`` and bind the
+        model to them; the views and scratch the conv backward of that mode reduces through."""
+        dev = self.device
+        named = [(n, tuple(p.shape)) for n, p in net.named_parameters()]
+        c1_replicas = {"conv1.grad_replicas": ((C1_NREP - 1) * C1_STRIDE,)}
+        if self.bwd_mode == "defer":
+            # gradient replicas in the flat buffer (replica 0 = the canonical slot), folded in fixed order
+            # by the optimizer's fold blocks: conv1 as 16 atomic-add replicas, conv2 as 16 image-group slabs
+            self.layout = FlatLayout(named, [FC_BUCKET, CONV_BUCKET + ["conv2.grad_replicas"]],
+                                     extra_shapes={**c1_replicas,
+                                                   "conv2.grad_replicas": ((C2_NREP - 1) * C2_STRIDE,)})
+        elif self.v2:
+            self.layout = FlatLayout(named, [FC_BUCKET, CONV_BUCKET_V2])
+        else:
+            self.layout = FlatLayout(named, [FC_BUCKET, CONV_BUCKET], extra_shapes=c1_replicas)
+        self.params, self.grads = self.layout.bind(net)
+        V, slots = self.layout.view, self.layout.slots
+        self.p = {n: V(self.params, n) for n in self.layout.param_names}
+        self.g = {n: V(self.grads, n) for n in self.layout.param_names}
+        self.off = o = {n: slots[n].offset for n in self.layout.param_names}
+        self.c1_off = c1 = o["conv1.weight"]
+        self.c2_off = c2 = o["conv2.weight"]
+        self.bucket_grads = [self.layout.bucket_view(self.grads, i) for i in range(2)]
+        self.bucket_ranges = [tuple(r) for r in self.layout.bucket_ranges]
+        assert self.bucket_ranges[0][0] == 0 and self.bucket_ranges[1][0] >= self.bucket_ranges[0][1]
+        assert o["conv1.bias"] == c1 + 512 and o["conv2.bias"] == c2 + 25024
+        if self.v2:
+            self.c1rep = torch.zeros(C1_NREP * C1_STRIDE, device=dev, dtype=torch.int64)   # kept zero by the kernel
+            self.tick = torch.zeros(32, device=dev, dtype=torch.int32)                      # arrival counters
+        if self.bwd_mode == "defer":
+            assert slots["conv1.grad_replicas"].offset == c1 + C1_STRIDE
+            assert slots["conv2.grad_replicas"].offset == c2 + C2_STRIDE
+            self.c1part = self.grads[c1: c1 + C1_NREP * C1_STRIDE]
+            self.slab = self.grads[c2: c2 + C2_NREP * C2_STRIDE]
+            self.zero_view = self.c1part              # zeroed by the conv forward (atomic targets)
+        elif self.v2:
+            assert c2 == c1 + C1_STRIDE
+            self.slab = torch.zeros(C2_NREP * C2_STRIDE, device=dev, dtype=torch.float32)
+            self.c1part = torch.zeros(C1_NREP * C1_STRIDE, device=dev, dtype=torch.float32)   # unused in fold mode
+            self.c1img = torch.zeros(self.B * 520, device=dev, dtype=torch.float32)          # ext mode
+            self.zero_view = None
+        else:
+            assert slots["conv1.grad_replicas"].offset == c1 + C1_STRIDE
+            self.g_c1w_rep = self.grads[c1: c1 + C1_NREP * C1_STRIDE]
+            self.g_c1b_rep = self.grads[c1 + 512: c1 + C1_NREP * C1_STRIDE]
+            self.zero_view = self.bucket_grads[1]
 
     # ------------------------------------------------------------------ learning-rate schedule
     def set_lr_table(self, table):
@@ -249,12 +290,13 @@ class LeNetTrainStep:
                                 self.Yb[self.q], self.rowsb[self.q])
 
     # ------------------------------------------------------------------ the step
-    def _opt(self, lo: int, hi: int, conv: bool, fuse_ar: Optional[str] = None):
-        """Fused optimizer update of the flat range [lo, hi) (one bucket or everything).  The conv
+    def _opt(self, lo: int = 0, hi: Optional[int] = None, conv: bool = True, fuse_ar: Optional[str] = None):
+        """Fused optimizer update of the flat range [lo, hi) (one bucket; by default everything).  The conv
         range carries the conv2 weight repack (Wp / Wt2) and, in the v1 layout, the conv1
         gradient-replica fold (v2 writes canonical gradients, nothing to fold).
         ``fuse_ar`` ('adam1' / 'adam2'): side blocks of the Adam kernel all-reduce the conv bucket
         (one- / two-shot peer protocol) while the other blocks update the fc parameters."""
+        hi = self.params.numel() if hi is None else hi
         K, sl = self.K, slice(lo, hi)
         pack_off = self.pack_off - lo if conv else -1
         pack, mode = (self.Wp, 2) if self.v2 else (self.Wt2, 1)
@@ -310,33 +352,151 @@ class LeNetTrainStep:
         n4 = self.grads.numel() // 4
         return (n4 + 2047) // 2048 <= min(256, 256 // max(1, getattr(peer, "shared", 1)))
 
-    def _conv_bwd2(self, B: int, q: int, fused_fc_route: Optional[str] = None, fold: bool = True):
-        """The v2 conv backward (+ the next batch's prefetch and the meters); ``fused_fc_route``
-        ('peer1' / 'peer2'): its W blocks also all-reduce the fc bucket across ranks once their own work
-        is done."""
-        p = self.p
-        kw = dict(row_loss=self.row_loss, row_hit=self.row_hit, loss_sum=self.loss_sum, correct=self.correct,
-                  gX=self.X, glabels=self.Y, gidx=self.idx, gctr=self.counters[1:], gnbatches=self.nbatches,
-                  gstride=self.B, gXdst=self.Xb[1 - q], gYdst=self.Yb[1 - q], grows=self.rowsb[1 - q],
-                  dbg=self.bwd_dbg)
-        if fused_fc_route is not None:
-            kw.update(peer_dev=self._peer_device_args(), ar_buf=self.bucket_grads[0],
-                      ar_two=int(fused_fc_route == "peer2"))
-        # the fused schedules' peer side blocks live in the in-launch "fold" kernel variant
-        mode = "fold" if fused_fc_route is not None else self.bwd_mode
-        kw["defer"] = {"fold": 0, "defer": 1, "ext": 2}[mode]
-        if mode == "ext":
-            kw["c1img"] = self.c1img
-        o = self.off
-        self.K.lenet_conv_bwd2(self.Xb[q], self.P1, self.A1, self.dP2m, self.A2, p["conv2.weight"], B, self.slab,
-                               self.c1rep, self.c1part, self.tick, self.grads, o["conv1.weight"], o["conv1.bias"],
-                               o["conv2.weight"], o["conv2.bias"], **kw)
-        if mode == "ext" and fold:   # canonical conv gradients (fixed-order sums) for the conv-bucket all-reduce
-            self.K.lenet_conv_grad_fold(self.slab, self.c1img, B, self.grads, o["conv1.weight"], o["conv1.bias"],
-                                        o["conv2.weight"], o["conv2.bias"])
+    def _forward(self, B: int, q: Optional[int], eval_batch=None):
+        """F1-F3: conv forward (v1 or v2) -> fc1 -> head.  A training step reads the batch prefetched
+        into parity ``q`` (v2) or gathers it (v1) and leaves dlogits, dZ1 and the per-row meters for the
+        backward; ``eval_batch`` = (workspace, images, labels) only adds to the eval meters.
+        Returns the (labels, rows) it used."""
+        K, p = self.K, self.p
+        train = eval_batch is None
+        ws, x, labels = (self.ws, None, None) if train else eval_batch
+        rows = None
+        if self.v2:
+            if train:
+                x, labels, rows = self.Xb[q], self.Yb[q], self.rowsb[q]
+            zero = (self.zero_view,) if train else ()
+            K.lenet_conv_fwd2(x, B, p["conv1.weight"], p["conv1.bias"], self.Wp, p["conv2.bias"], ws.P1, ws.A1,
+                              ws.P2, ws.A2, *zero)
+        else:
+            gather, out = (x, None, None, 0, 0, None), (None, None, None)
+            if train:
+                labels, rows = self.cur_lbl, self.cur_row
+                gather = (self.X, self.idx, self.counters[1:], self.nbatches, self.B, self.Y)
+                out = (rows, labels, self.zero_view)
+            K.lenet_conv_fwd(*gather, B, p["conv1.weight"], p["conv1.bias"], self.Wt2, p["conv2.bias"], ws.P1,
+                             ws.A1, ws.P2, ws.A2, *out)
+        K.lenet_fc1_fwd(ws.P2, B, p["fc1.weight"], p["fc1.bias"], ws.H1, self.counters if train else None)   # bumps counters
+        outs = ((ws.dZ2, ws.dZ1, self.row_loss, self.row_hit, None, None) if train else
+                (None, None, None, None, self.eval_loss, self.eval_correct))
+        K.lenet_head(ws.H1, B, p["fc2.weight"], p["fc2.bias"], labels, 1.0 / B, None, *outs)
+        return labels, rows
+
+    def _fc_backward(self, B: int):
+        """B1: after it bucket 0 (the fc gradients) is complete."""
+        ws, g = self.ws, self.g
+        # the loss / accuracy meters are folded by an extra block of conv_bwd (off fc_bwd's chain)
+        self.K.lenet_fc_bwd(ws.P2, ws.H1, ws.dZ1, ws.dZ2, self.p["fc1.weight"], B, ws.dP2m, g["fc1.weight"],
+                            g["fc1.bias"], g["fc2.weight"], g["fc2.bias"], None, None, None, None)
+
+    def _conv_backward(self, B: int, q: int, fused_fc_route: Optional[str] = None, fold: bool = True):
+        """B2: the conv backward (+ the meters; v2: + the next batch's prefetch into parity 1 - q);
+        ``fused_fc_route`` ('peer1' / 'peer2'): its W blocks also all-reduce the fc bucket across ranks
+        once their own work is done.  ``fold=False`` leaves the "ext" partials unfolded (``_fold_ar``)."""
+        K, ws, p, g, o = self.K, self.ws, self.p, self.g, self.off
+        if not self.v2:
+            peer = () if fused_fc_route is None else (0, self._peer_device_args(), self.bucket_grads[0],
+                                                      int(fused_fc_route == "peer2"))
+            K.lenet_conv_bwd(self.X, self.cur_row, ws.P1, ws.A1, ws.dP2m, ws.A2, p["conv2.weight"], B,
+                             self.g_c1w_rep, self.g_c1b_rep, g["conv2.weight"], g["conv2.bias"], C1_NREP, C1_STRIDE,
+                             self.row_loss, self.row_hit, self.loss_sum, self.correct, *peer)
+        else:
+            kw = dict(row_loss=self.row_loss, row_hit=self.row_hit, loss_sum=self.loss_sum, correct=self.correct,
+                      gX=self.X, glabels=self.Y, gidx=self.idx, gctr=self.counters[1:], gnbatches=self.nbatches,
+                      gstride=self.B, gXdst=self.Xb[1 - q], gYdst=self.Yb[1 - q], grows=self.rowsb[1 - q],
+                      dbg=self.bwd_dbg)
+            if fused_fc_route is not None:
+                kw.update(peer_dev=self._peer_device_args(), ar_buf=self.bucket_grads[0],
+                          ar_two=int(fused_fc_route == "peer2"))
+            # the fused schedules' peer side blocks live in the in-launch "fold" kernel variant
+            mode = "fold" if fused_fc_route is not None else self.bwd_mode
+            kw["defer"] = {"fold": 0, "defer": 1, "ext": 2}[mode]
+            if mode == "ext":
+                kw["c1img"] = self.c1img
+            K.lenet_conv_bwd2(self.Xb[q], ws.P1, ws.A1, ws.dP2m, ws.A2, p["conv2.weight"], B, self.slab, self.c1rep,
+                              self.c1part, self.tick, self.grads, o["conv1.weight"], o["conv1.bias"],
+                              o["conv2.weight"], o["conv2.bias"], **kw)
+            if mode == "ext" and fold:   # canonical conv gradients (fixed-order sums) for the conv-bucket all-reduce
+                K.lenet_conv_grad_fold(self.slab, self.c1img, B, self.grads, o["conv1.weight"], o["conv1.bias"],
+                                       o["conv2.weight"], o["conv2.bias"])
+
+    def _current_schedule(self) -> Schedule:
+        """Read at launch time: tests and the benchmark set ``mode`` / ``comm.routes`` directly."""
+        return Schedule(self.mode, self.comm.routes)
+
+    def _reduce_on_comm(self, cur, event: str, buf: torch.Tensor):
+        """All-reduce ``buf`` on the comm stream behind what the compute stream ``cur`` holds so far."""
+        ev, cs = self._ev[event], self.comm_stream
+        ev.record(cur)
+        cs.wait_event(ev)
+        with torch.cuda.stream(cs):
+            self.comm.all_reduce_(buf)
+
+    # one method per schedule mode (MODES): everything after the fc backward
+    def _step_none(self, B: int, q: int):
+        self._conv_backward(B, q)
+        self._opt()
+
+    def _step_serial(self, B: int, q: int):
+        route = self._current_schedule().route(self.grads)
+        pfold = route in ("pfold", "pfold2")
+        self._conv_backward(B, q, fold=not pfold)
+        if pfold:
+            self._fold_ar(B, two=route == "pfold2")   # fold + all-reduce in one launch
+        else:
+            self.comm.all_reduce_(self.grads)
+        self._opt()
+
+    def _step_flat(self, B: int, q: int):
+        cur = torch.cuda.current_stream(self.device)
+        self._conv_backward(B, q)
+        self._reduce_on_comm(cur, "conv", self.grads)
+        cur.wait_stream(self.comm_stream)
+        self._opt()
+
+    def _step_overlap(self, B: int, q: int):
+        cur = torch.cuda.current_stream(self.device)
+        ev, cs = self._ev, self.comm_stream
+        self._reduce_on_comm(cur, "fc", self.bucket_grads[0])
+        self._conv_backward(B, q)
+        ev["conv"].record(cur)
+        cs.wait_event(ev["conv"])
+        # the fc-bucket update (94 % of the parameters) runs while the conv bucket is being reduced
+        ev["fc_done"].record(cs)
+        with torch.cuda.stream(cs):
+            self.comm.all_reduce_(self.bucket_grads[1])
+        (a0, a1), (b0, b1) = self.bucket_ranges
+        cur.wait_event(ev["fc_done"])
+        self._opt(a0, a1, False)
+        cur.wait_stream(cs)
+        self._opt(b0, b1, True)
+
+    def _step_overlap2(self, B: int, q: int):
+        cur = torch.cuda.current_stream(self.device)
+        self._reduce_on_comm(cur, "fc", self.bucket_grads[0])
+        self._conv_backward(B, q)
+        # three cross-stream edges per step instead of four: both buckets are reduced on the comm
+        # stream (one communicator, one stream: collectives stay ordered), then ONE join before the
+        # whole optimizer (no separate fc-range update beside the conv bucket's reduction)
+        self._reduce_on_comm(cur, "conv", self.bucket_grads[1])
+        cur.wait_stream(self.comm_stream)
+        self._opt()
+
+    def _step_fused(self, B: int, q: int):
+        sched = self._current_schedule()
+        self._conv_backward(B, q, fused_fc_route=sched.route(self.bucket_grads[0], "peer2"))
+        conv_route = sched.route(self.bucket_grads[1], "rccl")
+        if conv_route in ("adam1", "adam2") and self.optimizer == "adam":
+            self._opt(fuse_ar=conv_route)
+        else:
+            self.comm.all_reduce_(self.bucket_grads[1])
+            self._opt()
+
+    _STEP = {"none": _step_none, "serial": _step_serial, "flat": _step_flat, "overlap": _step_overlap,
+             "overlap2": _step_overlap2, "fused": _step_fused}
 
     def _launch(self, B: int):
-        """One step on the current stream: conv_fwd -> fc1 -> head -> fc_bwd -> conv_bwd -> opt.
+        """One step on the current stream: conv_fwd -> fc1 -> head -> fc_bwd, then the schedule mode's
+        method: conv_bwd -> opt, with the all-reduces between them or beside conv_bwd.
 
         With a comm group and ``overlap``, bucket 0 (fc grads, complete after fc_bwd) is all-reduced
         on the comm stream while conv_bwd runs; bucket 1 after conv_bwd; the optimizer waits for both.
@@ -360,96 +520,12 @@ class LeNetTrainStep:
         grid-wide barrier (one agent-scope atomic counter, co-resident blocks) measures 3.6 us at 128
         blocks and 10.4 us at 256 against 1.5-1.6 us for a kernel boundary in a stream or hipGraph
         (tools/native/grid_barrier_bench.hip, profiles/r2_lenet_v3/grid_barrier_vs_kernel_boundary.jsonl).)"""
-        K, p, g = self.K, self.p, self.g
         q = self.q
-        if self.v2:
-            K.lenet_conv_fwd2(self.Xb[q], B, p["conv1.weight"], p["conv1.bias"], self.Wp, p["conv2.bias"], self.P1,
-                              self.A1, self.P2, self.A2, self.zero_view)
-            rows, labels = self.rowsb[q], self.Yb[q]
-        else:
-            K.lenet_conv_fwd(self.X, self.idx, self.counters[1:], self.nbatches, self.B, self.Y, B,
-                             p["conv1.weight"], p["conv1.bias"], self.Wt2, p["conv2.bias"], self.P1, self.A1, self.P2,
-                             self.A2, self.cur_row, self.cur_lbl, self.bucket_grads[1])
-            rows, labels = self.cur_row, self.cur_lbl
-        K.lenet_fc1_fwd(self.P2, B, p["fc1.weight"], p["fc1.bias"], self.H1, self.counters)   # bumps counters
-        K.lenet_head(self.H1, B, p["fc2.weight"], p["fc2.bias"], labels, 1.0 / B, None, self.dZ2, self.dZ1,
-                     self.row_loss, self.row_hit, None, None)
+        self._forward(B, q)
         if self.v2:
             self.q = 1 - q
-        fused = self.comm_on and self.mode == "fused"
-        # the loss / accuracy meters are folded by an extra block of conv_bwd (off fc_bwd's chain)
-        fc_args = (self.P2, self.H1, self.dZ1, self.dZ2, p["fc1.weight"], B, self.dP2m, g["fc1.weight"],
-                   g["fc1.bias"], g["fc2.weight"], g["fc2.bias"], None, None, None, None)
-        cur = torch.cuda.current_stream(self.device)
-        ev, cs = self._ev, self.comm_stream
-        K.lenet_fc_bwd(*fc_args)
-        pfold = (self.comm.routes.get(self.grads.numel()) if self.comm_on and self.mode == "serial" else None)
-        pfold = pfold if pfold in ("pfold", "pfold2") else None
-        if self.v2:
-            conv_bwd = lambda: self._conv_bwd2(B, q, fold=not pfold)
-        else:
-            conv_args = (self.X, rows, self.P1, self.A1, self.dP2m, self.A2, p["conv2.weight"], B,
-                         self.g_c1w_rep, self.g_c1b_rep, g["conv2.weight"], g["conv2.bias"], C1_NREP, C1_STRIDE,
-                         self.row_loss, self.row_hit, self.loss_sum, self.correct)
-            conv_bwd = lambda: K.lenet_conv_bwd(*conv_args)
-        if fused:
-            fc_route = self.comm.routes.get(self.bucket_grads[0].numel(), "peer2")
-            if self.v2:
-                self._conv_bwd2(B, q, fused_fc_route=fc_route)
-            else:
-                K.lenet_conv_bwd(*conv_args, 0, self._peer_device_args(), self.bucket_grads[0],
-                                 int(fc_route == "peer2"))
-            conv_route = self.comm.routes.get(self.bucket_grads[1].numel(), "rccl")
-            if conv_route in ("adam1", "adam2") and self.optimizer == "adam":
-                self._opt(0, self.params.numel(), True, fuse_ar=conv_route)
-            else:
-                self.comm.all_reduce_(self.bucket_grads[1])
-                self._opt(0, self.params.numel(), True)
-            return
-        if self.comm_on and self.mode in ("overlap", "overlap2"):
-            ev["fc"].record(cur)
-            cs.wait_event(ev["fc"])
-            with torch.cuda.stream(cs):
-                self.comm.all_reduce_(self.bucket_grads[0])
-        conv_bwd()
-        if self.comm_on and self.mode == "overlap2":
-            # three cross-stream edges per step instead of four: both buckets are reduced on the comm
-            # stream (one communicator, one stream: collectives stay ordered), then ONE join before the
-            # whole optimizer (no separate fc-range update beside the conv bucket's reduction)
-            ev["conv"].record(cur)
-            cs.wait_event(ev["conv"])
-            with torch.cuda.stream(cs):
-                self.comm.all_reduce_(self.bucket_grads[1])
-            cur.wait_stream(cs)
-            self._opt(0, self.params.numel(), True)
-            return
-        if not self.comm_on or self.mode == "none":     # "none": the comm path's compute alone (autotune probe)
-            self._opt(0, self.params.numel(), True)
-            return
-        if self.mode == "serial":
-            if pfold:
-                self._fold_ar(B, two=pfold == "pfold2")   # fold + all-reduce in one launch
-            else:
-                self.comm.all_reduce_(self.grads)
-            self._opt(0, self.params.numel(), True)
-            return
-        ev["conv"].record(cur)
-        cs.wait_event(ev["conv"])
-        if self.mode == "flat":
-            with torch.cuda.stream(cs):
-                self.comm.all_reduce_(self.grads)
-            cur.wait_stream(cs)
-            self._opt(0, self.params.numel(), True)
-            return
-        # the fc-bucket update (94 % of the parameters) runs while the conv bucket is being reduced
-        ev["fc_done"].record(cs)
-        with torch.cuda.stream(cs):
-            self.comm.all_reduce_(self.bucket_grads[1])
-        (a0, a1), (b0, b1) = self.bucket_ranges
-        cur.wait_event(ev["fc_done"])
-        self._opt(a0, a1, False)
-        cur.wait_stream(cs)
-        self._opt(b0, b1, True)
+        self._fc_backward(B)
+        self._STEP[self.mode if self.comm_on else "none"](self, B, q)
 
     def _peer_device_args(self):
         if self._peer_dev is None:
@@ -563,29 +639,16 @@ class LeNetTrainStep:
     @torch.no_grad()
     def evaluate(self, images: torch.Tensor, labels: torch.Tensor, batch_size: Optional[int] = None):
         """Forward-only pass over a (device) test set with the fused kernels; returns (loss_sum, correct, n)."""
-        K, p = self.K, self.p
         bs = batch_size or self.B
         X = images.reshape(images.shape[0], 784).contiguous()
         Y = labels.to(torch.int64).contiguous()
         n = X.shape[0]
         self.eval_loss.zero_()
         self.eval_correct.zero_()
-        P1 = torch.empty(bs * 2880, device=self.device)
-        A1 = torch.empty(bs * 2880, device=self.device, dtype=torch.uint8)
-        P2 = torch.empty(bs * 800, device=self.device)
-        A2 = torch.empty(bs * 800, device=self.device, dtype=torch.uint8)
-        H1 = torch.empty(bs * 500, device=self.device)
+        ws = LeNetWorkspace(bs, self.device)
         for s in range(0, n, bs):
             B = min(bs, n - s)
-            if self.v2:
-                K.lenet_conv_fwd2(X[s:s + B], B, p["conv1.weight"], p["conv1.bias"], self.Wp, p["conv2.bias"], P1,
-                                  A1, P2, A2)
-            else:
-                K.lenet_conv_fwd(X[s:s + B], None, None, 0, 0, None, B, p["conv1.weight"], p["conv1.bias"],
-                                 self.Wt2, p["conv2.bias"], P1, A1, P2, A2, None, None, None)
-            K.lenet_fc1_fwd(P2, B, p["fc1.weight"], p["fc1.bias"], H1, None)
-            K.lenet_head(H1, B, p["fc2.weight"], p["fc2.bias"], Y[s:s + B], 1.0 / B, None, None, None,
-                         None, None, self.eval_loss, self.eval_correct)
+            self._forward(B, None, eval_batch=(ws, X[s:s + B], Y[s:s + B]))
         return float(self.eval_loss.item()), int(self.eval_correct.item()), n
 
     # ------------------------------------------------------------------ optimizer state (torch format)
@@ -633,40 +696,64 @@ class LeNetTrainStep:
 
     # ------------------------------------------------------------------ schedule autotuning (W > 1)
     def set_schedule(self, label: str):
-        """Force one schedule by its autotuner label, e.g. ``"serial 431296:peer1"`` or
-        ``"overlap2 25664:peer1,405632:rccl"`` (mode, then bucket numel:route pairs); identically on
-        every rank (traces / A/B runs)."""
-        mode, _, rest = label.strip().partition(" ")
-        routes = {int(n): r for n, r in (kv.split(":") for kv in rest.split(",") if kv)}
-        if mode not in ("overlap", "overlap2", "flat", "serial", "fused", "none"):
-            raise ValueError(f"unknown schedule mode {mode!r}")
-        self.mode = mode
-        self.comm.routes = routes
+        """Force one schedule by its autotuner label (``Schedule.parse``), e.g. ``"serial 431296:peer1"``;
+        identically on every rank (traces / A/B runs)."""
+        sched = Schedule.parse(label)
+        self.mode, self.comm.routes = sched.mode, sched.routes
         self.graphs.clear()
 
     def schedule_candidates(self):
-        """(mode, {bucket numel: route}) pairs the comm path can run: bucketed + overlapped with the
-        conv backward (one route per bucket), or one all-reduce after backward on the comm stream
-        ("flat") or on the compute stream ("serial"), one route each."""
-        routes = ["rccl"] if self.comm.group.rccl is not None else []
-        if getattr(self.comm, "peer", None) is not None:
-            routes += ["peer1", "peer2"]
+        """The ``Schedule``s the comm path can run: bucketed + overlapped with the conv backward
+        ("overlap" / "overlap2", one route per bucket), or one all-reduce after backward on the comm
+        stream ("flat") or on the compute stream ("serial"), one route each; with the peer kernel also
+        "serial" with the fold + all-reduce launch where ``pfold_ok``, and "fused" (fc bucket peer1 /
+        peer2 inside the conv backward, conv bucket by any route or, with Adam, inside the optimizer)."""
+        has_peer = getattr(self.comm, "peer", None) is not None
+        routes = (["rccl"] if self.comm.group.rccl is not None else []) + (["peer1", "peer2"] if has_peer else [])
         n0, n1, nall = (self.bucket_grads[0].numel(), self.bucket_grads[1].numel(), self.grads.numel())
-        out = [("overlap", {n0: a, n1: b}) for a in routes for b in routes]
-        out += [("overlap2", {n0: a, n1: b}) for a in routes for b in routes]
-        out += [(m, {nall: a}) for m in ("flat", "serial") for a in routes]
-        if getattr(self.comm, "peer", None) is not None:
+        out = [Schedule(m, {n0: a, n1: b}) for m in ("overlap", "overlap2") for a in routes for b in routes]
+        out += [Schedule(m, {nall: a}) for m in ("flat", "serial") for a in routes]
+        if has_peer:
             if self.pfold_ok():
-                out += [("serial", {nall: "pfold"})]     # fold + in-place one-shot in one launch
+                out += [Schedule("serial", {nall: "pfold"})]     # fold + in-place one-shot in one launch
             if self.pfold_ok(two=True) and self.world > 1:
-                out += [("serial", {nall: "pfold2"})]    # fold + in-place two-shot in one launch
-        if getattr(self.comm, "peer", None) is not None:
-            out += [("fused", {n0: a, n1: b}) for a in ("peer1", "peer2") for b in routes]
+                out += [Schedule("serial", {nall: "pfold2"})]    # fold + in-place two-shot in one launch
+            out += [Schedule("fused", {n0: a, n1: b}) for a in ("peer1", "peer2") for b in routes]
             if self.optimizer == "adam":         # last: a failing candidate poisons the peer protocol
-                out += [("fused", {n0: a, n1: b}) for a in ("peer1", "peer2") for b in ("adam1", "adam2")]
+                out += [Schedule("fused", {n0: a, n1: b}) for a in ("peer1", "peer2") for b in ("adam1", "adam2")]
         # RCCL-only schedules first: they are timed even if the budget or the peer protocol runs out
-        uses_peer = lambda c: c[0] == "fused" or any(r != "rccl" for r in c[1].values())
-        return sorted(out, key=uses_peer)
+        return sorted(out, key=lambda c: c.uses_peer)
+
+    def _snapshot(self):
+        """Clones of the model / optimizer / data-position state that trial steps advance, and the parity."""
+        # counters[0] is also the index into an attached learning-rate table: restoring it restores the
+        # schedule position, so the trial steps do not consume the schedule
+        state = [self.params, self.m, self.counters, self.Xb, self.Yb, self.rowsb] + (
+            [self.v] if self.v is not self.m else [])
+        return [(t, t.clone()) for t in state], self.q
+
+    def _restore(self, snap):
+        tensors, self.q = snap
+        for t, t0 in tensors:
+            t.copy_(t0)
+        self.ar_epoch.fill_(-1)              # optimizer steps repeat: no stale completion word
+        self.sync_params()
+
+    def _time_replays(self, graph_steps: int, reps: int) -> float:
+        """us per step of ``reps`` replays of a ``graph_steps``-step hipGraph of the schedule now set,
+        captured afresh and warmed by one replay; all ranks start the timed replays together."""
+        self.graphs.clear()
+        self.capture(steps=graph_steps)
+        self.replay(steps=graph_steps)               # warm
+        torch.cuda.synchronize(self.device)
+        self.comm.group.host.barrier()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(reps):
+            self.replay(steps=graph_steps)
+        e.record()
+        torch.cuda.synchronize(self.device)
+        return s.elapsed_time(e) * 1e3 / (reps * graph_steps)
 
     def autotune_schedule(self, steps: int = 40, graph_steps: int = 10, candidates=None,
                           budget_s: float = 60.0):
@@ -686,57 +773,34 @@ class LeNetTrainStep:
         on every rank; if no candidate survives, the RCCL-only "overlap" schedule is kept."""
         if not self.comm_on:
             return {}
-        cands = candidates or self.schedule_candidates()
-        # counters[0] is also the index into an attached learning-rate table: restoring it restores the
-        # schedule position, so the trial steps do not consume the schedule
-        state = [self.params, self.m, self.counters, self.Xb, self.Yb, self.rowsb] + (
-            [self.v] if self.v is not self.m else [])
-        snap = [t.clone() for t in state]
-        q_saved = self.q
-        saved_idx = None if self.idx is None else (self.idx, self.nfull, self.tail, self.nbatches)
         if self.idx is None or self.nfull < 1:
             raise RuntimeError("bind a dataset and set epoch indices before autotune_schedule")
+        cands = [Schedule(*c) for c in candidates or self.schedule_candidates()]
+        snap = self._snapshot()
+        saved_idx = (self.idx, self.nfull, self.tail, self.nbatches)
         g = self.comm.group
         times, invalid = [], []
         peer = getattr(self.comm, "peer", None)
         wd = g.watchdog
-        import time as _time
-        t_start = _time.perf_counter()
-        for mode, routes in cands:
-            el = torch.tensor([_time.perf_counter() - t_start], dtype=torch.float64)
+        reps = max(1, steps // graph_steps)
+        t_start = time.perf_counter()
+        for sched in cands:
+            el = torch.tensor([time.perf_counter() - t_start], dtype=torch.float64)
             g.host.allreduce(el.data_ptr(), 1, 1, 3)          # float64 MAX: one decision for all ranks
             if el.item() > budget_s:
                 times.append(float("inf"))
                 invalid.append(1)
                 continue
-            uses_peer = mode == "fused" or any(r != "rccl" for r in routes.values())
             perr0 = peer.error() if peer is not None else 0
             anyerr = torch.tensor([perr0], dtype=torch.int64)
             g.host.allreduce(anyerr.data_ptr(), 1, 3, 3)      # collective decision: every rank skips alike
-            if uses_peer and anyerr.item():      # a timed-out peer protocol is poisoned: never pick it
+            if sched.uses_peer and anyerr.item():      # a timed-out peer protocol is poisoned: never pick it
                 times.append(float("inf"))
                 invalid.append(1)
                 continue
-            for t, s0 in zip(state, snap):       # every candidate starts from the same (replicated) state
-                t.copy_(s0)
-            self.q = q_saved
-            self.ar_epoch.fill_(-1)              # optimizer steps repeat: no stale completion word
-            self.sync_params()
-            self.mode = mode
-            self.comm.routes = dict(routes)
-            self.graphs.clear()
-            self.capture(steps=graph_steps)
-            reps = max(1, steps // graph_steps)
-            self.replay(steps=graph_steps)               # warm
-            torch.cuda.synchronize(self.device)
-            g.host.barrier()
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(reps):
-                self.replay(steps=graph_steps)
-            e.record()
-            torch.cuda.synchronize(self.device)
-            times.append(s.elapsed_time(e) * 1e3 / (reps * graph_steps))
+            self._restore(snap)                  # every candidate starts from the same (replicated) state
+            self.mode, self.comm.routes = sched.mode, dict(sched.routes)
+            times.append(self._time_replays(graph_steps, reps))
             # safety net: a schedule must leave every replica bit-identical and report no comm error
             bits = self.params.view(torch.int32).to(torch.int64).sum().item()
             failed = (peer is not None and peer.error() > perr0) or (wd is not None and bool(wd.error()))
@@ -748,24 +812,9 @@ class LeNetTrainStep:
         # the same step with the collectives left out (never selectable): what the communication adds
         # on top of the comm path's compute (a W > 1 scaling point decomposes into the two)
         self.compute_only_us = None
-        for tt, s0 in zip(state, snap):
-            tt.copy_(s0)
-        self.q = q_saved
-        self.sync_params()
+        self._restore(snap)
         self.mode = "none"
-        self.graphs.clear()
-        self.capture(steps=graph_steps)
-        self.replay(steps=graph_steps)
-        torch.cuda.synchronize(self.device)
-        g.host.barrier()
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        reps = max(1, steps // graph_steps)
-        s.record()
-        for _ in range(reps):
-            self.replay(steps=graph_steps)
-        e.record()
-        torch.cuda.synchronize(self.device)
-        co = torch.tensor([s.elapsed_time(e) * 1e3 / (reps * graph_steps)], dtype=torch.float64)
+        co = torch.tensor([self._time_replays(graph_steps, reps)], dtype=torch.float64)
         g.host.allreduce(co.data_ptr(), 1, 1, 3)
         self.compute_only_us = round(float(co.item()), 2)
         t = torch.tensor(times, dtype=torch.float64)
@@ -777,26 +826,21 @@ class LeNetTrainStep:
             if g.rccl is None:
                 raise RuntimeError("no communication schedule kept the replicas identical (comm failure?)")
             n0, n1 = self.bucket_grads[0].numel(), self.bucket_grads[1].numel()
-            cands = list(cands) + [("overlap", {n0: "rccl", n1: "rccl"})]   # bounded fallback: RCCL only
+            cands.append(Schedule("overlap", {n0: "rccl", n1: "rccl"}))   # bounded fallback: RCCL only
             times.append(0.0)
         # a schedule with cross-stream edges (overlap / flat) must win by > 1 %: in a replayed hipGraph
         # every such edge adds 5-9 us of jitter-prone join latency (round 3: flat 61.9 us in the
         # autotuner, 68.3 us in the timed window; the single-stream serial schedule measured 62.0)
-        eff = [x * (1.01 if cands[i][0] in ("overlap", "overlap2", "flat") else 1.0) for i, x in enumerate(times)]
-        best = min(range(len(cands)), key=lambda i: eff[i])
-        self.mode, self.comm.routes = cands[best][0], dict(cands[best][1])
+        eff = [x * (1.01 if c.cross_stream else 1.0) for c, x in zip(cands, times)]
+        best = cands[eff.index(min(eff))]
+        self.mode, self.comm.routes = best.mode, dict(best.routes)
         self.graphs.clear()
-        # restore the training state the trial steps advanced
-        for t, s0 in zip(state, snap):
-            t.copy_(s0)
-        self.q = q_saved
-        self.ar_epoch.fill_(-1)
-        self.sync_params()
+        self._restore(snap)                      # the training state the trial steps advanced
         self.idx, self.nfull, self.tail, self.nbatches = saved_idx
         self.loss_sum.zero_()
         self.correct.zero_()
         torch.cuda.synchronize(self.device)
-        label = lambda c: c[0] + " " + ",".join(f"{n}:{r}" for n, r in sorted(c[1].items()))
-        self.schedule_times = {label(c): (round(x, 2) if x != float("inf") else None) for c, x in zip(cands, times)}
-        self.schedule = label(cands[best])
+        self.schedule_times = {c.label(): (round(x, 2) if x != float("inf") else None)
+                               for c, x in zip(cands, times)}
+        self.schedule = best.label()
         return self.schedule_times
