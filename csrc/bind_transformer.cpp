@@ -130,8 +130,10 @@ void xent_bf16(const at::Tensor& logits, const at::Tensor& tgt, int64_t V, doubl
             "xent_bf16");
 }
 
+// doc_start / doc_end (packed sequences, ops/transformer.py doc_bounds): int32 [B, T]; the position of
+// row (b, t) is t - doc_start[b, t], and the backward walks each row's documents through doc_end
 void embed_fwd(const at::Tensor& idx, const at::Tensor& wte, const at::Tensor& wpe, const at::Tensor& out, int64_t T,
-               const OptT& rng, int64_t site, int64_t thr, double inv_keep) {
+               const OptT& rng, int64_t site, int64_t thr, double inv_keep, const OptT& doc_start) {
   check_cuda(idx, "idx", I64);
   const int64_t N = idx.numel(), C = wte.size(1);
   TORCH_CHECK(C % 4 == 0 && N % T == 0 && wpe.size(0) >= T, "embed: bad shapes");
@@ -139,16 +141,17 @@ void embed_fwd(const at::Tensor& idx, const at::Tensor& wte, const at::Tensor& w
   check_cuda(wpe, "wpe", BF16);
   check_cuda(out, "out", BF16, N * C);
   hip_check(pde_embed_fwd(ptr<int64_t>(idx), wte.data_ptr(), wpe.data_ptr(), out.data_ptr(), (int)N, (int)T, (int)C,
-                          drop_of(rng, site, thr, inv_keep), cur_stream()),
+                          drop_of(rng, site, thr, inv_keep), optr<int>(doc_start, "doc_start", I32, N), cur_stream()),
             "embed_fwd");
 }
 
 void embed_bwd(const at::Tensor& dX, const at::Tensor& idx, const at::Tensor& dwte, const at::Tensor& dwpe,
                const at::Tensor& acc, const at::Tensor& touched, int64_t T, bool accumulate_pos, const OptT& rng,
-               int64_t site, int64_t thr, double inv_keep) {
+               int64_t site, int64_t thr, double inv_keep, const OptT& doc_end) {
   check_cuda(idx, "idx", I64);
   const int64_t N = idx.numel(), C = dwte.size(1), Vp = dwte.size(0);
   TORCH_CHECK(C % 4 == 0, "embed: C must be a multiple of 4");
+  TORCH_CHECK(T > 0 && N % T == 0, "embed: idx must hold whole rows of T");
   check_cuda(dX, "dX", BF16, N * C);
   check_cuda(dwte, "dwte", BF16);
   check_cuda(dwpe, "dwpe", BF16, T * C);
@@ -156,8 +159,18 @@ void embed_bwd(const at::Tensor& dX, const at::Tensor& idx, const at::Tensor& dw
   check_cuda(touched, "touched", U8, Vp);
   hip_check(pde_embed_bwd(dX.data_ptr(), ptr<int64_t>(idx), dwte.data_ptr(), dwpe.data_ptr(), ptr<float>(acc),
                           ptr<uint8_t>(touched), (int)N, (int)T, (int)C, (int)Vp, accumulate_pos,
-                          drop_of(rng, site, thr, inv_keep), cur_stream()),
+                          drop_of(rng, site, thr, inv_keep), optr<int>(doc_end, "doc_end", I32, N), cur_stream()),
             "embed_bwd");
+}
+
+// bounds (int32 [2, B, T]) <- first / last position of the document holding t, from doc_ids (int64 [B, T])
+void doc_bounds(const at::Tensor& doc_ids, const at::Tensor& bounds) {
+  check_cuda(doc_ids, "doc_ids", I64);
+  TORCH_CHECK(doc_ids.dim() == 2 && doc_ids.size(1) >= 1, "doc_ids must be [B, T]");
+  const int64_t N = doc_ids.numel(), T = doc_ids.size(1);
+  TORCH_CHECK(N <= INT32_MAX / 2, "doc_bounds: too many positions");
+  check_cuda(bounds, "bounds", I32, 2 * N);
+  hip_check(pde_doc_bounds(ptr<int64_t>(doc_ids), ptr<int>(bounds), (int)N, (int)T, cur_stream()), "doc_bounds");
 }
 
 void sumsq_bf16(const at::Tensor& g, double scale, const at::Tensor& out, const OptT& step_inc) {
@@ -249,7 +262,7 @@ void check_qkv(const at::Tensor& t, const char* name, int64_t B, int64_t T, int6
 
 void attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
               const at::Tensor& lse, int64_t H, double scale, const OptT& rng, int64_t site, int64_t thr,
-              double inv_keep) {
+              double inv_keep, const OptT& doc_start) {
   const int64_t B = q.size(0), T = q.size(1);
   TORCH_CHECK(T % 128 == 0, "attention: T must be a multiple of 128");
   check_qkv(q, "q", B, T, H);
@@ -260,15 +273,18 @@ void attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, con
   check_cuda(lse, "lse", F32, B * H * T);
   hip_check(pde_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), (int)q.stride(1), o.data_ptr(), (int)o.stride(1),
                          ptr<float>(lse), (int)B, (int)T, (int)H, (float)scale, drop_of(rng, site, thr, inv_keep, 8),
-                         cur_stream()),
+                         optr<int>(doc_start, "doc_start", I32, B * T), cur_stream()),
             "attn_fwd");
 }
 
 void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
               const at::Tensor& dout, const at::Tensor& lse, const at::Tensor& Dd, const at::Tensor& dq,
               const at::Tensor& dk, const at::Tensor& dv, int64_t H, double scale, const OptT& rng, int64_t site,
-              int64_t thr, double inv_keep) {
+              int64_t thr, double inv_keep, const OptT& doc_start, const OptT& doc_end) {
   const int64_t B = q.size(0), T = q.size(1);
+  const int* ds = optr<int>(doc_start, "doc_start", I32, B * T);
+  const int* de = optr<int>(doc_end, "doc_end", I32, B * T);
+  TORCH_CHECK((ds == nullptr) == (de == nullptr), "attn_bwd: doc_start and doc_end go together");
   TORCH_CHECK(T % 128 == 0, "attention: T must be a multiple of 128");
   for (auto* p : {&q, &k, &v, &dq, &dk, &dv}) check_qkv(*p, "q/k/v/dq/dk/dv", B, T, H);
   for (auto* p : {&k, &v, &dq, &dk, &dv})
@@ -281,7 +297,7 @@ void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, con
   hip_check(pde_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), (int)q.stride(1), o.data_ptr(), dout.data_ptr(),
                          (int)o.stride(1), ptr<float>(lse), ptr<float>(Dd), dq.data_ptr(), dk.data_ptr(),
                          dv.data_ptr(), (int)B, (int)T, (int)H, (float)scale, drop_of(rng, site, thr, inv_keep, 8),
-                         cur_stream()),
+                         ds, de, cur_stream()),
             "attn_bwd");
 }
 
@@ -358,9 +374,12 @@ void register_transformer(pybind11::module& m) {
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd", &gelu_bwd);
   m.def("xent_bf16", &xent_bf16);
-  m.def("embed_fwd", &embed_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe"), py::arg("out"), py::arg("T"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
+  m.def("embed_fwd", &embed_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe"), py::arg("out"), py::arg("T"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0,
+        py::arg("doc_start") = py::none());
   m.def("embed_bwd", &embed_bwd, py::arg("dX"), py::arg("idx"), py::arg("dwte"), py::arg("dwpe"), py::arg("acc"),
-        py::arg("touched"), py::arg("T"), py::arg("accumulate_pos"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
+        py::arg("touched"), py::arg("T"), py::arg("accumulate_pos"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0,
+        py::arg("doc_end") = py::none());
+  m.def("doc_bounds", &doc_bounds);
   m.def("sumsq_bf16", &sumsq_bf16, py::arg("g"), py::arg("scale"), py::arg("out"), py::arg("step_inc") = py::none());
   m.def("adamw_master", &adamw_master, py::arg("master"), py::arg("p16"), py::arg("g16"), py::arg("m"), py::arg("v"),
         py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("grad_scale"),
@@ -373,9 +392,11 @@ void register_transformer(pybind11::module& m) {
   m.def("colsum_bf16_splits", &colsum_bf16_splits);
   m.def("colsum_bf16", &colsum_bf16);
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("H"),
-        py::arg("scale"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
+        py::arg("scale"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0,
+        py::arg("doc_start") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"), py::arg("lse"),
-        py::arg("D"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("H"), py::arg("scale"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
+        py::arg("D"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("H"), py::arg("scale"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0,
+        py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none());
   m.def("attn_set_variant", [](int64_t v) { pde_attn_set_variant((int)v); });
 }
 

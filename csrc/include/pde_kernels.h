@@ -150,10 +150,15 @@ hipError_t pde_gelu_fwd(const void* X, void* Y, int64_t n, hipStream_t st);
 hipError_t pde_gelu_bwd(const void* dY, const void* X, void* dX, int64_t n, hipStream_t st);
 hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
                          int write_grad, hipStream_t st);
+// doc_start / doc_end (nullable, int32 [N]): packed sequences.  The forward reads wpe[t - doc_start[row]],
+// the backward sums dX into dwpe by that position, walking each row's documents through doc_end.
 hipError_t pde_embed_fwd(const int64_t* idx, const void* wte, const void* wpe, void* out, int N, int T, int C,
-                         PdeDrop drop, hipStream_t st);
+                         PdeDrop drop, const int* doc_start, hipStream_t st);
 hipError_t pde_embed_bwd(const void* dX, const int64_t* idx, void* dwte, void* dwpe, float* acc, uint8_t* touched,
-                         int N, int T, int C, int Vp, int accumulate_pos, PdeDrop drop, hipStream_t st);
+                         int N, int T, int C, int Vp, int accumulate_pos, PdeDrop drop, const int* doc_end,
+                         hipStream_t st);
+// doc_ids [N = B * T] -> bounds [2, N]: first / last position (in its row of T) of the document holding t
+hipError_t pde_doc_bounds(const int64_t* doc_ids, int* bounds, int N, int T, hipStream_t st);
 hipError_t pde_sumsq_bf16(const void* g, int64_t n, float scale, float* out, float* step_inc, hipStream_t st);
 hipError_t pde_adamw_master(float* master, void* p16, const void* g16, float* m, float* v, int64_t n, float lr,
                             float b1, float b2, float eps, float wd, float grad_scale, int step,
@@ -209,11 +214,13 @@ hipError_t pde_gemm_reduce(const float* part, int S, int M, int N, void* dw, con
 // ---- attention (attention.hip) ----
 void pde_attn_set_variant(int v);
 // drop.rng != nullptr: dropout on the attention probabilities (the DROP instantiations of the kernels)
+// doc_start / doc_end (nullable, int32 [B, T], both or neither in the backward): packed sequences, key k is
+// visible to query q iff doc_start[b, q] <= k <= q (the DOC instantiations of the kernels)
 hipError_t pde_attn_fwd(const void* q, const void* k, const void* v, int ldq, void* o, int ldo, float* lse, int B,
-                        int T, int H, float scale, PdeDrop drop, hipStream_t st);
+                        int T, int H, float scale, PdeDrop drop, const int* doc_start, hipStream_t st);
 hipError_t pde_attn_bwd(const void* q, const void* k, const void* v, int ldq, const void* o, const void* dout,
                         int ldo, const float* lse, float* Dd, void* dq, void* dk, void* dv, int B, int T, int H,
-                        float scale, PdeDrop drop, hipStream_t st);
+                        float scale, PdeDrop drop, const int* doc_start, const int* doc_end, hipStream_t st);
 
 
 // ---- resnet (resnet.hip) ----

@@ -35,6 +35,18 @@
 // LSE use the undropped probabilities, only the P fragment fed to the V^T P^T MFMA is masked, and
 // 1 / keep is folded into the final 1 / l multiply.  Backward: dS = P o (M o dP / keep - D) with
 // D = rowsum(dO o O) as before (O is the dropped output), and dV takes the masked, scaled P.
+//
+// Packed sequences are the DOC template parameter; the DOC = false instantiations are the code above,
+// unchanged.  dstart[b, t] / dend[b, t] (int32) are the first and last position of the document that
+// holds t, both non-decreasing in t, and key k is visible to query q iff dstart[b, q] <= k <= q, which
+// for well-formed bounds is k <= q <= dend[b, k] (the form the dK/dV kernel uses: one value per key
+// lane).  A forward / dQ block starts its key loop at the tile of dstart[first query of the block], a
+// dK/dV block ends its query loop after the tile of dend[last key of the block]; both bounds are read
+// with block-uniform loads and clamped into the causal tile range, so malformed bounds give wrong
+// numbers but never a tile outside [0, T).  Inside the loop a wave skips a tile that lies wholly before
+// its first query's document (dK/dV: wholly after its last key's), masks per element only the tiles a
+// document start (end) can cut, and the forward's running max is guarded: a query whose 64 keys of a
+// tile are all masked keeps m = -inf and takes exp2(-inf - 0) = 0, not exp2(-inf - -inf).
 #include <type_traits>
 
 #include "pde_hip.h"
@@ -159,6 +171,60 @@ struct AttnDrop {
   __device__ __forceinline__ bool kept(uint32_t word, int e) const { return ((word >> (8 * e)) & 0xffu) >= thr; }
 };
 
+// ------------------------------------------------------------------------------------ documents
+// Document view of a forward / dQ wave (queries q0 .. q0 + 31 of block qt, this lane's query myq).
+// DOC = false: every member folds to the causal-only constant.
+template <bool DOC>
+struct DocQuery {
+  int first_tile = 0;   // block-uniform: first 64-key tile any query of the block sees
+  int lo = 0, hi = 0;   // wave-uniform: dstart of the wave's first / last query (its min / max)
+  int mine = 0;         // dstart of this lane's query
+  __device__ __forceinline__ DocQuery(const int* __restrict__ dstart, int b, int T, int qt, int q0, int myq) {
+    if constexpr (DOC) {
+      const int* d = dstart + (size_t)b * T;
+      first_tile = min(max(__builtin_amdgcn_readfirstlane(d[qt * 128]), 0) >> 6, 2 * qt);
+      lo = __builtin_amdgcn_readfirstlane(d[q0]);
+      hi = __builtin_amdgcn_readfirstlane(d[q0 + 31]);
+      mine = d[myq];
+    }
+  }
+  // some query of the wave sees some key of the tile at k0 (as far as documents go)
+  __device__ __forceinline__ bool wave_sees(int k0) const { return !DOC || k0 + 63 >= lo; }
+  // a document start of one of the wave's queries lies past the tile's first key
+  __device__ __forceinline__ bool cuts(int k0) const { return DOC && hi > k0; }
+  // key > q or key < dstart[q]; with documents, as one unsigned compare of offsets from dstart[q]
+  __device__ __forceinline__ bool hidden(int key, int q) const {
+    if constexpr (DOC) return (uint32_t)(key - mine) > (uint32_t)(q - mine);
+    else return key > q;
+  }
+};
+
+// Document view of a dK/dV wave (keys k0 .. k0 + 31 of block kb, this lane's key myk).
+template <bool DOC>
+struct DocKey {
+  int end_tile;         // block-uniform: one past the last 64-query tile that sees a key of the block
+  int lo = 0, hi = 0;   // wave-uniform: dend of the wave's first / last key (its min / max)
+  int mine = 0;         // dend of this lane's key
+  __device__ __forceinline__ DocKey(const int* __restrict__ dend, int b, int T, int kb, int k0, int myk) {
+    end_tile = T / 64;
+    if constexpr (DOC) {
+      const int* d = dend + (size_t)b * T;
+      end_tile = min(max((__builtin_amdgcn_readfirstlane(d[kb * 128 + 127]) >> 6) + 1, 2 * kb + 2), T / 64);
+      lo = __builtin_amdgcn_readfirstlane(d[k0]);
+      hi = __builtin_amdgcn_readfirstlane(d[k0 + 31]);
+      mine = d[myk];
+    }
+  }
+  __device__ __forceinline__ bool wave_seen(int qbase) const { return !DOC || qbase <= hi; }
+  // a document end of one of the wave's keys lies before the last of the 32 queries from qfirst
+  __device__ __forceinline__ bool cuts(int qfirst) const { return DOC && qfirst + 31 > lo; }
+  // key > q or q > dend[key]
+  __device__ __forceinline__ bool hidden(int key, int q) const {
+    if constexpr (DOC) return (uint32_t)(q - key) > (uint32_t)(mine - key);
+    else return key > q;
+  }
+};
+
 // ------------------------------------------------------------------------------------ block map
 // (tile, batch*head) of this block.  The dispatcher deals blocks to the 8 XCDs round-robin, so with a
 // plain 2-D grid the tiles of one (batch, head) land on every XCD and each XCD re-fetches that head's
@@ -179,11 +245,12 @@ __device__ __forceinline__ void attn_block(int nt, int nbh, int G, bool heavy_hi
 
 // ------------------------------------------------------------------------------------ forward
 // grid (T/128 * B*H), 256 threads: wave w owns queries qt*128 + 32w + (0..31)
-template <int NST, int OCC, bool DROP>
+template <int NST, int OCC, bool DROP, bool DOC>
 __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                      const bf16_t* __restrict__ V, int ldq, bf16_t* __restrict__ O,
                                                      int ldo, float* __restrict__ LSE, int T, int H, float sl2,
-                                                     float scale, int G, PdeDrop drop) {
+                                                     float scale, int G, PdeDrop drop,
+                                                     const int* __restrict__ dstart) {
   __shared__ __attribute__((aligned(16))) char lds[NST * 2 * TILE];  // stage: K | V
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h = lane >> 5, r = lane & 31;
   int qt, bh;
@@ -196,6 +263,8 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict_
   const int q0 = qt * 128 + w * 32, myq = q0 + r;
   const int nkt = (qt * 128 + 127) / 64 + 1;
   const int last_kt = (q0 + 31) / 64;
+  const DocQuery<DOC> doc(dstart, b, T, qt, q0, myq);
+  const int kt0 = doc.first_tile;
   auto issue = [&](int kt) {
     const char* st = lds + (kt % NST) * 2 * TILE;
     issue_tile(kr, ldq, kt * 64, st, w, lrow, lch);
@@ -206,16 +275,16 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict_
   for (int s = 0; s < 4; ++s) qf[s] = ld16(Q + boff + (size_t)myq * ldq + 16 * s + 8 * h);
 #pragma unroll
   for (int s = 0; s < NST - 1; ++s)
-    if (s < nkt) issue(s);
+    if (kt0 + s < nkt) issue(kt0 + s);
   const uint2 tl = tr_lane_off();
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char*)lds;
   f32x16 o0 = {}, o1 = {};
   float m = -INFINITY, l = 0.f;
-  for (int kt = 0; kt < nkt; ++kt) {
+  for (int kt = kt0; kt < nkt; ++kt) {
     wait_stages<4>(min(NST - 2, nkt - 1 - kt));
     __builtin_amdgcn_s_barrier();
     if (kt + NST - 1 < nkt) issue(kt + NST - 1);
-    if (kt <= last_kt) {
+    if (kt <= last_kt && doc.wave_sees(kt * 64)) {
       const int sb = kt % NST;
       const char* Ks = lds + sb * 2 * TILE;
       const uint2 vb = add2(tl, lds0 + sb * 2 * TILE + TILE);
@@ -229,12 +298,12 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict_
       // V^T fragments in flight while the softmax runs
       const bf16x8 v00 = tfrag<0, 0>(vb), v01 = tfrag<0, 1>(vb), v10 = tfrag<1, 0>(vb), v11 = tfrag<1, 1>(vb);
       const bf16x8 v20 = tfrag<2, 0>(vb), v21 = tfrag<2, 1>(vb), v30 = tfrag<3, 0>(vb), v31 = tfrag<3, 1>(vb);
-      if (k0 + 63 > q0) {  // tile crosses the diagonal of this wave
+      if (k0 + 63 > q0 || doc.cuts(k0)) {  // tile crosses the diagonal of this wave, or a document start
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int key = k0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-          s0[i] = key > myq ? -INFINITY : s0[i];
-          s1[i] = key + 32 > myq ? -INFINITY : s1[i];
+          s0[i] = doc.hidden(key, myq) ? -INFINITY : s0[i];
+          s1[i] = doc.hidden(key + 32, myq) ? -INFINITY : s1[i];
         }
       }
       float mx = -INFINITY;
@@ -243,7 +312,8 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict_
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
       const float mn = fmaxf(m, mx);
       if (__any(mn > m)) {                 // some query's running max grew: rescale O and l
-        const float alpha = fexp2((m - mn) * sl2);
+        float alpha = fexp2((m - mn) * sl2);
+        if constexpr (DOC) alpha = mn == -INFINITY ? 1.f : alpha;   // a query that has seen no key yet
         l *= alpha;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -252,7 +322,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict_
         }
         m = mn;
       }
-      const float mb = m * sl2;
+      const float mb = (DOC && m == -INFINITY) ? 0.f : m * sl2;
       float ls = 0.f;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
@@ -299,13 +369,14 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd(const bf16_t* __restrict_
 // Dd[bh, t] = sum_d dO * O of its query rows is computed here, from the dO fragments it loads anyway
 // plus the O rows (each lane pair holds a row's 64 dims), and written for k_attn_bwd_dkdv, which runs
 // after it: no separate pre-pass over dO and O (14.6 us per layer at the GPT-2 shape).
-template <int NST, int OCC, bool DROP>
+template <int NST, int OCC, bool DROP, bool DOC>
 __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                         const bf16_t* __restrict__ V, int ldq,
                                                         const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO,
                                                         int ldo, const float* __restrict__ LSE,
                                                         float* __restrict__ Dd, bf16_t* __restrict__ dQ, int T, int H,
-                                                        float sl2, float scale, int G, PdeDrop drop) {
+                                                        float sl2, float scale, int G, PdeDrop drop,
+                                                        const int* __restrict__ dstart) {
   __shared__ __attribute__((aligned(16))) char lds[NST * 2 * TILE];  // stage: K | V
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h = lane >> 5, r = lane & 31;
   int qt, bh;
@@ -319,6 +390,8 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(const bf16_t* __restri
   const int q0 = qt * 128 + w * 32, myq = q0 + r;
   const int nkt = (qt * 128 + 127) / 64 + 1;
   const int last_kt = (q0 + 31) / 64;
+  const DocQuery<DOC> doc(dstart, b, T, qt, q0, myq);
+  const int kt0 = doc.first_tile;
   auto issue = [&](int kt) {
     const char* st = lds + (kt % NST) * 2 * TILE;
     issue_tile(kr, ldq, kt * 64, st, w, lrow, lch);
@@ -342,15 +415,15 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(const bf16_t* __restri
   if (h == 0) Dd[(size_t)bh * T + myq] = dq_d;
 #pragma unroll
   for (int s = 0; s < NST - 1; ++s)
-    if (s < nkt) issue(s);
+    if (kt0 + s < nkt) issue(kt0 + s);
   const uint2 tl = tr_lane_off();
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char*)lds;
   f32x16 a0 = {}, a1 = {};
-  for (int kt = 0; kt < nkt; ++kt) {
+  for (int kt = kt0; kt < nkt; ++kt) {
     wait_stages<4>(min(NST - 2, nkt - 1 - kt));
     __builtin_amdgcn_s_barrier();
     if (kt + NST - 1 < nkt) issue(kt + NST - 1);
-    if (kt <= last_kt) {
+    if (kt <= last_kt && doc.wave_sees(kt * 64)) {
       const int sb = kt % NST;
       const char* Ks = lds + sb * 2 * TILE;
       const char* Vs = Ks + TILE;
@@ -366,7 +439,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(const bf16_t* __restri
       }
       const bf16x8 k00 = tfrag<0, 0>(kb), k01 = tfrag<0, 1>(kb), k10 = tfrag<1, 0>(kb), k11 = tfrag<1, 1>(kb);
       const bf16x8 k20 = tfrag<2, 0>(kb), k21 = tfrag<2, 1>(kb), k30 = tfrag<3, 0>(kb), k31 = tfrag<3, 1>(kb);
-      const bool diag = k0 + 63 > q0;
+      const bool diag = k0 + 63 > q0 || doc.cuts(k0);
       if constexpr (DROP) {   // dP <- M o dP / keep
         const AttnDrop ad(drop);
         uint32_t w0[4], w1[4];
@@ -386,8 +459,8 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(const bf16_t* __restri
         float p0 = fexp2(fmaf(s0[i], sl2, -lse2));
         float p1 = fexp2(fmaf(s1[i], sl2, -lse2));
         if (diag) {
-          p0 = key > myq ? 0.f : p0;
-          p1 = key + 32 > myq ? 0.f : p1;
+          p0 = doc.hidden(key, myq) ? 0.f : p0;
+          p1 = doc.hidden(key + 32, myq) ? 0.f : p1;
         }
         s0[i] = p0 * (d0[i] - dq_d);
         s1[i] = p1 * (d1[i] - dq_d);
@@ -410,14 +483,15 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq(const bf16_t* __restri
 // dK, dV: grid (T/128 * B*H); wave w owns keys kb*128 + 32w + (0..31); loops over 64-query tiles
 // with Q / dO / LSE / D staged in LDS (rows for S / dP, transposed reads for dK / dV).
 constexpr int kDkdvStage = 2 * TILE + 512;           // Q | dO | LSE[64] | D[64]
-template <int NST, int OCC, bool DROP>
+template <int NST, int OCC, bool DROP, bool DOC>
 __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                           const bf16_t* __restrict__ V, int ldq,
                                                           const bf16_t* __restrict__ dO, int ldo,
                                                           const float* __restrict__ LSE,
                                                           const float* __restrict__ Dd, bf16_t* __restrict__ dK,
                                                           bf16_t* __restrict__ dV, int T, int H, float sl2,
-                                                          float scale, int G, PdeDrop drop) {
+                                                          float scale, int G, PdeDrop drop,
+                                                          const int* __restrict__ dend) {
   __shared__ __attribute__((aligned(16))) char lds[NST * kDkdvStage];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h = lane >> 5, r = lane & 31;
   int kb, bh;
@@ -430,7 +504,9 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __rest
   const rsrc_t vecr = make_rsrc((w & 1) ? Dd + (size_t)bh * T : LSE + (size_t)bh * T, (uint32_t)T * 4);
   const int lrow = glds_row(lane), lch = glds_chunk(lane, w & 1);
   const int k0 = kb * 128 + w * 32, myk = k0 + r;
-  const int qt0 = (kb * 128) / 64, nqt = T / 64;
+  const int qt0 = (kb * 128) / 64;
+  const DocKey<DOC> doc(dend, b, T, kb, k0, myk);
+  const int nqt = doc.end_tile;
   auto issue = [&](int qt) {
     const char* st = lds + ((qt - qt0) % NST) * kDkdvStage;
     issue_tile(qr, ldq, qt * 64, st, w, lrow, lch);
@@ -456,7 +532,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __rest
     __builtin_amdgcn_s_barrier();
     if (qt + NST - 1 < nqt) issue(qt + NST - 1);
     const int qbase = qt * 64;
-    if (k0 <= qbase + 63) {  // some query of this tile sees some key of this wave
+    if (k0 <= qbase + 63 && doc.wave_seen(qbase)) {  // some query of this tile sees some key of this wave
       const int sb = (qt - qt0) % NST;
       const char* Qs = lds + sb * kDkdvStage;
       const char* Gs = Qs + TILE;
@@ -481,7 +557,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __rest
         }
         // the causal mask only matters where this wave's keys reach past the half's first query
         // (wave-uniform): the other tiles skip the per-element compare / select
-        const bool need_mask = k0 + 31 > qbase + 32 * u;
+        const bool need_mask = k0 + 31 > qbase + 32 * u || doc.cuts(qbase + 32 * u);
         uint32_t kws[4] = {0u, 0u, 0u, 0u};
         if constexpr (DROP) AttnDrop(drop).key_words(bh, T, qbase + 32 * u + 4 * h, myk, kws);
         auto softmax_grad = [&](auto MASK_) {
@@ -500,7 +576,7 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __rest
               float p = fexp2(fmaf(S[i], sl2, -lv[e]));
               if constexpr (MASK) {
                 const int q = qbase + 32 * u + 8 * g + 4 * h + e;
-                p = myk > q ? 0.f : p;
+                p = doc.hidden(myk, q) ? 0.f : p;
               }
               if constexpr (DROP) {   // dV takes the masked, scaled P; dS = P o (M o dP / keep - D)
                 const bool keep = ((kw >> (8 * e)) & 0xffu) >= drop.thr;
@@ -545,30 +621,30 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dkdv(const bf16_t* __rest
 int g_attn_variant = 5;   // pde_attn_set_variant: LDS ring depth / occupancy (default: measured best)
 int g_attn_group = kAttnGroup;   // heads per L2 group of the block map (0: plain order)
 
-template <int NST, int OCC, bool DROP>
+template <int NST, int OCC, bool DROP, bool DOC = false>
 void launch_fwd(const void* q, const void* k, const void* v, int ldq, void* o, int ldo, float* lse, int B, int T,
-                int H, float scale, PdeDrop drop, hipStream_t st) {
-  hipLaunchKernelGGL((k_attn_fwd<NST, OCC, DROP>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
+                int H, float scale, PdeDrop drop, hipStream_t st, const int* dstart = nullptr) {
+  hipLaunchKernelGGL((k_attn_fwd<NST, OCC, DROP, DOC>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, ldq, (bf16_t*)o, ldo, lse, T, H, scale * 1.4426950408889634f,
-                     scale, g_attn_group, drop);
+                     scale, g_attn_group, drop, dstart);
 }
 
-template <int NST, int OCC, bool DROP>
+template <int NST, int OCC, bool DROP, bool DOC = false>
 void launch_dq(const void* q, const void* k, const void* v, int ldq, const void* o, const void* dout, int ldo,
                const float* lse, float* Dd, void* dq, int B, int T, int H, float sl2, float scale, PdeDrop drop,
-               hipStream_t st) {
-  hipLaunchKernelGGL((k_attn_bwd_dq<NST, OCC, DROP>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
+               hipStream_t st, const int* dstart = nullptr) {
+  hipLaunchKernelGGL((k_attn_bwd_dq<NST, OCC, DROP, DOC>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, ldq, (const bf16_t*)o, (const bf16_t*)dout, ldo, lse, Dd,
-                     (bf16_t*)dq, T, H, sl2, scale, g_attn_group, drop);
+                     (bf16_t*)dq, T, H, sl2, scale, g_attn_group, drop, dstart);
 }
 
-template <int NST, int OCC, bool DROP>
+template <int NST, int OCC, bool DROP, bool DOC = false>
 void launch_dkdv(const void* q, const void* k, const void* v, int ldq, const void* dout, int ldo, const float* lse,
                  const float* Dd, void* dk, void* dv, int B, int T, int H, float sl2, float scale, PdeDrop drop,
-                 hipStream_t st) {
-  hipLaunchKernelGGL((k_attn_bwd_dkdv<NST, OCC, DROP>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
+                 hipStream_t st, const int* dend = nullptr) {
+  hipLaunchKernelGGL((k_attn_bwd_dkdv<NST, OCC, DROP, DOC>), dim3(T / 128 * B * H), dim3(256), 0, st, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, ldq, (const bf16_t*)dout, ldo, lse, Dd, (bf16_t*)dk,
-                     (bf16_t*)dv, T, H, sl2, scale, g_attn_group, drop);
+                     (bf16_t*)dv, T, H, sl2, scale, g_attn_group, drop, dend);
 }
 
 }  // namespace
@@ -579,6 +655,7 @@ extern "C" {
 //               4 = dK/dV with a 3-deep ring (2 blocks per CU).  Default 5, measured on MI355X at the
 //               GPT-2 shape (tools/attn_bench.py, profiles/r2_attn/): fwd 85.3 -> 71.3 us, bwd 263.8 -> 241.0 us
 //               bits 8..15: heads per L2 group of the block map (attn_block), 0 = default, 255 = plain order
+// The document-masked (DOC) instantiations exist for the default 5 only and ignore the low bits.
 void pde_attn_set_variant(int v) {
   g_attn_variant = v & 0xff;
   const int g = (v >> 8) & 0xff;
@@ -586,8 +663,13 @@ void pde_attn_set_variant(int v) {
 }
 
 hipError_t pde_attn_fwd(const void* q, const void* k, const void* v, int ldq, void* o, int ldo, float* lse, int B,
-                        int T, int H, float scale, PdeDrop drop, hipStream_t st) {
+                        int T, int H, float scale, PdeDrop drop, const int* doc_start, hipStream_t st) {
   if (T % 128 != 0) return hipErrorInvalidValue;
+  if (doc_start) {   // packed sequences: the default ring depth / occupancy of the plain forward
+    if (drop.rng) launch_fwd<3, 3, true, true>(q, k, v, ldq, o, ldo, lse, B, T, H, scale, drop, st, doc_start);
+    else launch_fwd<3, 3, false, true>(q, k, v, ldq, o, ldo, lse, B, T, H, scale, drop, st, doc_start);
+    return hipGetLastError();
+  }
   if (drop.rng) {   // same ring depth / occupancy choice as the undropped forward (152 VGPRs: 3 blocks per CU fit)
     if (g_attn_variant & 1) launch_fwd<3, 3, true>(q, k, v, ldq, o, ldo, lse, B, T, H, scale, drop, st);
     else launch_fwd<kNstDefault, 2, true>(q, k, v, ldq, o, ldo, lse, B, T, H, scale, drop, st);
@@ -598,10 +680,23 @@ hipError_t pde_attn_fwd(const void* q, const void* k, const void* v, int ldq, vo
 
 hipError_t pde_attn_bwd(const void* q, const void* k, const void* v, int ldq, const void* o, const void* dout,
                         int ldo, const float* lse, float* Dd, void* dq, void* dk, void* dv, int B, int T, int H,
-                        float scale, PdeDrop drop, hipStream_t st) {
+                        float scale, PdeDrop drop, const int* doc_start, const int* doc_end, hipStream_t st) {
   if (T % 128 != 0) return hipErrorInvalidValue;
+  if ((doc_start == nullptr) != (doc_end == nullptr)) return hipErrorInvalidValue;
   const float sl2 = scale * 1.4426950408889634f;
   // dQ first: it computes and writes Dd (= rowsum dO * O), which the dK / dV kernel reads
+  if (doc_start) {   // packed sequences: dQ <4, 2> and dK/dV <3, 2>, the defaults of the plain backward
+    if (drop.rng) {
+      launch_dq<kNstDefault, 2, true, true>(q, k, v, ldq, o, dout, ldo, lse, Dd, dq, B, T, H, sl2, scale, drop, st,
+                                            doc_start);
+      launch_dkdv<3, 2, true, true>(q, k, v, ldq, dout, ldo, lse, Dd, dk, dv, B, T, H, sl2, scale, drop, st, doc_end);
+    } else {
+      launch_dq<kNstDefault, 2, false, true>(q, k, v, ldq, o, dout, ldo, lse, Dd, dq, B, T, H, sl2, scale, drop, st,
+                                             doc_start);
+      launch_dkdv<3, 2, false, true>(q, k, v, ldq, dout, ldo, lse, Dd, dk, dv, B, T, H, sl2, scale, drop, st, doc_end);
+    }
+    return hipGetLastError();
+  }
   if (drop.rng) {   // dQ at 2 blocks per CU (224 VGPRs), dK/dV with the default 3-deep ring (231 VGPRs)
     launch_dq<kNstDefault, 2, true>(q, k, v, ldq, o, dout, ldo, lse, Dd, dq, B, T, H, sl2, scale, drop, st);
     launch_dkdv<3, 2, true>(q, k, v, ldq, dout, ldo, lse, Dd, dk, dv, B, T, H, sl2, scale, drop, st);

@@ -562,15 +562,18 @@ __global__ __launch_bounds__(256) void k_xent_bf16(bf16_t* __restrict__ L, const
 
 // ---------------------------------------------------------------------------------- embeddings
 // DROP: embedding dropout applied while writing (element index = offset in the [N, C] output)
-template <bool DROP>
+// DOC: packed sequences, the position restarts at every document: pos = t - dstart[row], clamped into
+// [0, t] so that malformed bounds never index outside wpe
+template <bool DROP, bool DOC>
 __global__ __launch_bounds__(256) void k_embed_fwd(const int64_t* __restrict__ idx, const bf16_t* __restrict__ wte,
                                                    const bf16_t* __restrict__ wpe, bf16_t* __restrict__ out, int N,
-                                                   int T, int C, PdeDrop drop) {
+                                                   int T, int C, PdeDrop drop, const int* __restrict__ dstart) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
   const int64_t tok = idx[row];
-  const int pos = row % T;
+  int pos = row % T;
+  if constexpr (DOC) pos -= min(max(dstart[row], 0), pos);
   const uint2* a = reinterpret_cast<const uint2*>(wte + (size_t)tok * C);
   const uint2* b = reinterpret_cast<const uint2*>(wpe + (size_t)pos * C);
   uint2* o = reinterpret_cast<uint2*>(out + (size_t)row * C);
@@ -610,6 +613,76 @@ __global__ __launch_bounds__(256) void k_embed_bwd_pos(const bf16_t* __restrict_
     for (int e = 0; e < 4; ++e) acc[e] += o[e];
   }
   *d = pack4(acc);
+}
+
+// Packed sequences: dwpe[p, :] = sum over every document of dX[b, doc start + p, :] (documents shorter
+// than p + 1 add nothing, so a row no position reaches is written as zero).  Thread per (p, 4-column
+// chunk) walks each row's documents through dend, which fixes the order of the sum: no atomics, the
+// same bits on every run.  A malformed dend is clamped into [s, T - 1]: the walk always advances and
+// never leaves the row.
+template <bool DROP>
+__global__ __launch_bounds__(256) void k_embed_bwd_pos_doc(const bf16_t* __restrict__ dX, bf16_t* __restrict__ dwpe,
+                                                           const int* __restrict__ dend, int N, int T, int C,
+                                                           int accumulate, PdeDrop drop) {
+  const int nc = C >> 2;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= T * nc) return;
+  const int p = i / nc, c = i % nc;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int r0 = 0; r0 < N; r0 += T) {
+    for (int s = 0; s < T;) {
+      const int e = min(max(dend[r0 + s], s), T - 1);
+      if (s + p <= e) {
+        const int r = r0 + s + p;
+        float x[4];
+        unpack4(reinterpret_cast<const uint2*>(dX + (size_t)r * C)[c], x);
+        if constexpr (DROP) DropSite(drop).apply((uint64_t)r * nc + c, x);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] += x[k];
+      }
+      s = e + 1;
+    }
+  }
+  uint2* d = reinterpret_cast<uint2*>(dwpe + (size_t)p * C) + c;
+  if (accumulate) {
+    float o[4];
+    unpack4(*d, o);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] += o[k];
+  }
+  *d = pack4(acc);
+}
+
+// doc_ids [B, T] -> bounds [2, B, T]: first and last position of the document holding t.  A document
+// starts at t = 0 and wherever the id changes.  One block per row: the waves ballot the starts into a
+// bitmap in LDS (bit t of word t / 64), then every position finds the nearest start at or before it
+// (its document's first position) and the nearest start after it (one past its last) with clz / ffs,
+// stepping over empty words.  Bit 0 is always set, so the backward search ends at word 0 at the latest.
+__global__ __launch_bounds__(256) void k_doc_bounds(const int64_t* __restrict__ ids, int* __restrict__ bounds, int N,
+                                                    int T) {
+  extern __shared__ unsigned long long doc_first[];
+  const int lane = threadIdx.x & 63, nw = (T + 63) >> 6;
+  const size_t r0 = (size_t)blockIdx.x * T;
+  const int64_t* row = ids + r0;
+  for (int t0 = threadIdx.x & ~63; t0 < T; t0 += 256) {      // wave-uniform bound: every lane votes
+    const int t = t0 + lane;
+    const unsigned long long m = __ballot(t < T && (t == 0 || row[t] != row[t - 1]));
+    if (lane == 0) doc_first[t0 >> 6] = m;
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < T; t += 256) {
+    const int bit = t & 63;
+    int w = t >> 6;
+    unsigned long long m = doc_first[w] & (~0ull >> (63 - bit));
+    while (m == 0) m = doc_first[--w];
+    const int s = (w << 6) + 63 - __clzll((long long)m);
+    w = t >> 6;
+    m = bit == 63 ? 0ull : doc_first[w] & (~0ull << (bit + 1));
+    while (m == 0 && ++w < nw) m = doc_first[w];
+    const int e = m ? (w << 6) + __ffsll((long long)m) - 2 : T - 1;
+    bounds[r0 + t] = s;
+    bounds[(size_t)N + r0 + t] = e;
+  }
 }
 
 // token rows: fp32 atomics into a scratch table + a per-row touched flag
@@ -995,26 +1068,46 @@ hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V,
 }
 
 hipError_t pde_embed_fwd(const int64_t* idx, const void* wte, const void* wpe, void* out, int N, int T, int C,
-                         PdeDrop drop, hipStream_t st) {
-  if (drop.rng)
-    hipLaunchKernelGGL(k_embed_fwd<true>, dim3((N + 3) / 4), dim3(256), 0, st, idx, (const bf16_t*)wte,
-                       (const bf16_t*)wpe, (bf16_t*)out, N, T, C, drop);
+                         PdeDrop drop, const int* doc_start, hipStream_t st) {
+  const dim3 grid((N + 3) / 4), blk(256);
+  const bf16_t* te = (const bf16_t*)wte;
+  const bf16_t* pe = (const bf16_t*)wpe;
+  if (doc_start) {
+    if (drop.rng) hipLaunchKernelGGL((k_embed_fwd<true, true>), grid, blk, 0, st, idx, te, pe, (bf16_t*)out, N, T, C, drop, doc_start);
+    else hipLaunchKernelGGL((k_embed_fwd<false, true>), grid, blk, 0, st, idx, te, pe, (bf16_t*)out, N, T, C, drop, doc_start);
+  } else if (drop.rng)
+    hipLaunchKernelGGL((k_embed_fwd<true, false>), grid, blk, 0, st, idx, te, pe, (bf16_t*)out, N, T, C, drop, doc_start);
   else
-    hipLaunchKernelGGL(k_embed_fwd<false>, dim3((N + 3) / 4), dim3(256), 0, st, idx, (const bf16_t*)wte,
-                       (const bf16_t*)wpe, (bf16_t*)out, N, T, C, drop);
+    hipLaunchKernelGGL((k_embed_fwd<false, false>), grid, blk, 0, st, idx, te, pe, (bf16_t*)out, N, T, C, drop, doc_start);
+  return hipGetLastError();
+}
+
+hipError_t pde_doc_bounds(const int64_t* doc_ids, int* bounds, int N, int T, hipStream_t st) {
+  if (T < 1 || N % T != 0 || T > 64 * 1024) return hipErrorInvalidValue;   // the bitmap: T / 8 bytes of LDS
+  if (N == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_doc_bounds, dim3(N / T), dim3(256), (size_t)((T + 63) / 64) * 8, st, doc_ids, bounds, N, T);
   return hipGetLastError();
 }
 
 hipError_t pde_embed_bwd(const void* dX, const int64_t* idx, void* dwte, void* dwpe, float* acc, uint8_t* touched,
-                         int N, int T, int C, int Vp, int accumulate_pos, PdeDrop drop, hipStream_t st) {
+                         int N, int T, int C, int Vp, int accumulate_pos, PdeDrop drop, const int* doc_end,
+                         hipStream_t st) {
   if (drop.rng) {
-    hipLaunchKernelGGL(k_embed_bwd_pos<true>, dim3((T * (C / 4) + 255) / 256), dim3(256), 0, st, (const bf16_t*)dX,
-                       (bf16_t*)dwpe, N, T, C, accumulate_pos, drop);
+    if (doc_end)
+      hipLaunchKernelGGL(k_embed_bwd_pos_doc<true>, dim3((T * (C / 4) + 255) / 256), dim3(256), 0, st,
+                         (const bf16_t*)dX, (bf16_t*)dwpe, doc_end, N, T, C, accumulate_pos, drop);
+    else
+      hipLaunchKernelGGL(k_embed_bwd_pos<true>, dim3((T * (C / 4) + 255) / 256), dim3(256), 0, st, (const bf16_t*)dX,
+                         (bf16_t*)dwpe, N, T, C, accumulate_pos, drop);
     hipLaunchKernelGGL(k_embed_bwd_tok<true>, dim3((N + 3) / 4), dim3(256), 0, st, (const bf16_t*)dX, idx, acc,
                        touched, N, C, drop);
   } else {
-    hipLaunchKernelGGL(k_embed_bwd_pos<false>, dim3((T * (C / 4) + 255) / 256), dim3(256), 0, st, (const bf16_t*)dX,
-                       (bf16_t*)dwpe, N, T, C, accumulate_pos, drop);
+    if (doc_end)
+      hipLaunchKernelGGL(k_embed_bwd_pos_doc<false>, dim3((T * (C / 4) + 255) / 256), dim3(256), 0, st,
+                         (const bf16_t*)dX, (bf16_t*)dwpe, doc_end, N, T, C, accumulate_pos, drop);
+    else
+      hipLaunchKernelGGL(k_embed_bwd_pos<false>, dim3((T * (C / 4) + 255) / 256), dim3(256), 0, st, (const bf16_t*)dX,
+                         (bf16_t*)dwpe, N, T, C, accumulate_pos, drop);
     hipLaunchKernelGGL(k_embed_bwd_tok<false>, dim3((N + 3) / 4), dim3(256), 0, st, (const bf16_t*)dX, idx, acc,
                        touched, N, C, drop);
   }

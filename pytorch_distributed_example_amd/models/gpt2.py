@@ -14,6 +14,11 @@ forward, and every site of that forward and its backward regenerates its mask fr
 numbered: embedding 0; layer ``l`` attention probabilities ``1 + 3l``, attention-projection output
 ``2 + 3l``, MLP output ``3 + 3l``.
 
+Packed sequences (``GPT.forward(idx, targets, doc_ids=)``): rows that hold several concatenated documents.
+``ops.doc_bounds`` turns the ids into per-position document bounds once per forward, on the device; the
+attention of every block masks keys outside the query's document (and skips key tiles no query of a block
+can see) and the embedding takes the position inside the document.  Generation never uses it.
+
 Generation (``GPT.generate``): the prompt goes once through the training kernels and fills a KV cache;
 every further token is one decode step over ``ops/decode.py`` (``DecodeSession``) whose per-token state
 lives on the device, so the step is captured once and replayed.  It uses a ``DeviceRNG`` of its own, never
@@ -76,7 +81,10 @@ class _Attn(tnn.Module):
         self.c_attn = _Linear(C, 3 * C, 0.02)
         self.c_proj = _Linear(C, C, 0.02 / math.sqrt(2 * cfg.n_layer))
 
-    def forward(self, x, snap=None, site=0):
+    def forward(self, x, snap=None, site=0, doc_bounds=None):
+        if doc_bounds is not None:      # packed sequences (ops.doc_bounds), with or without dropout
+            p = 0.0 if snap is None else self.attn_pdrop
+            return self.c_proj(T.causal_attention(self.c_attn(x), self.n_head, p, snap, site, doc_bounds=doc_bounds))
         if snap is None or self.attn_pdrop == 0.0:
             return self.c_proj(T.causal_attention(self.c_attn(x), self.n_head))
         return self.c_proj(T.causal_attention(self.c_attn(x), self.n_head, self.attn_pdrop, snap, site))
@@ -106,20 +114,21 @@ class Block(tnn.Module):
     def forward(self, x, delta=None):
         return sum(self.forward_deferred(x, delta))
 
-    def forward_deferred(self, x, delta=None, snap=None):
+    def forward_deferred(self, x, delta=None, snap=None, doc_bounds=None):
         """(residual, mlp_out) with the block output = residual + mlp_out left unsummed, so the next
         LayerNorm adds it inside its kernel.  ``delta`` is the previous block's deferred mlp_out.
         (residual, LN(x)) come from one op: the residual-gradient add is fused into the LN backward.
         ``snap`` (an RNG snapshot of this forward) turns dropout on: the returned mlp_out is still
         undropped -- whoever adds it drops it under this layer's site ``3 + 3l``, as this block does
-        with the ``delta`` it is handed."""
+        with the ``delta`` it is handed.  ``doc_bounds`` (``ops.doc_bounds``) masks attention per document."""
         if snap is not None:
-            return self._forward_deferred_drop(x, delta, snap)
+            return self._forward_deferred_drop(x, delta, snap, doc_bounds)
         if delta is None:
             x, h = T.layer_norm_residual(x, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
         else:
             x, h = T.add_layer_norm_residual(x, delta, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
-        x, h = T.add_layer_norm_residual(x, self.attn(h), self.ln_2.weight, self.ln_2.bias, self.ln_2.eps)
+        x, h = T.add_layer_norm_residual(x, self.attn(h, doc_bounds=doc_bounds), self.ln_2.weight, self.ln_2.bias,
+                                         self.ln_2.eps)
         return x, self.mlp(h)
 
     def forward_deferred_qkv(self, x, delta=None):
@@ -148,15 +157,15 @@ class Block(tnn.Module):
         f = D.skinny_linear(h, self.mlp.c_fc.weight, self.mlp.c_fc.bias, gelu=True)
         return x, D.skinny_linear(f, self.mlp.c_proj.weight, self.mlp.c_proj.bias)
 
-    def _forward_deferred_drop(self, x, delta, snap):
+    def _forward_deferred_drop(self, x, delta, snap, doc_bounds=None):
         l, p = self.layer_idx, self.resid_pdrop
         if delta is None:
             x, h = T.layer_norm_residual(x, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
         else:
             x, h = T.add_dropout_layer_norm_residual(x, delta, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps,
                                                      p, snap, 3 * l)          # = 3 + 3(l - 1)
-        x, h = T.add_dropout_layer_norm_residual(x, self.attn(h, snap, 1 + 3 * l), self.ln_2.weight, self.ln_2.bias,
-                                                 self.ln_2.eps, p, snap, 2 + 3 * l)
+        x, h = T.add_dropout_layer_norm_residual(x, self.attn(h, snap, 1 + 3 * l, doc_bounds), self.ln_2.weight,
+                                                 self.ln_2.bias, self.ln_2.eps, p, snap, 2 + 3 * l)
         return x, self.mlp(h)
 
 
@@ -202,17 +211,30 @@ class GPT(tnn.Module):
         c = self.config
         return self.training and (c.embd_pdrop > 0.0 or c.attn_pdrop > 0.0 or c.resid_pdrop > 0.0)
 
-    def forward(self, idx, targets=None):
+    def forward(self, idx, targets=None, doc_ids=None):
+        """Logits ``[B, T, V]``, or the mean cross-entropy against ``targets``.
+
+        ``doc_ids`` (an integer ``[B, T]`` tensor on the model's device) marks packed rows: a document
+        begins at ``t = 0`` and wherever ``doc_ids[b, t] != doc_ids[b, t - 1]``.  Every token then attends
+        to its own document only and takes the learned position of its offset inside that document, so
+        each document is computed as if it stood alone at the start of a row.  The loss is still the mean
+        over all ``B * T`` targets, the one after each document's last token included.  ``None`` is the
+        call as it was."""
         t = self.transformer
+        # computed once, on the device, and handed to the embedding and to every block
+        bounds = None if doc_ids is None else T.doc_bounds(doc_ids)
         # one draw per training forward, before its first site; none at all when dropout is off
         snap = self.rng.next() if self.dropout_active() else None
-        if snap is None:
+        if bounds is not None:
+            x = T.embedding(idx, t.wte.weight, t.wpe.weight, 0.0 if snap is None else self.config.embd_pdrop, snap, 0,
+                            doc_bounds=bounds)
+        elif snap is None:
             x = T.embedding(idx, t.wte.weight, t.wpe.weight)
         else:
             x = T.embedding(idx, t.wte.weight, t.wpe.weight, self.config.embd_pdrop, snap, 0)
         delta = None
         for blk in t.h:
-            x, delta = blk.forward_deferred(x, delta, snap)
+            x, delta = blk.forward_deferred(x, delta, snap, bounds)
         if delta is None:
             x = t.ln_f(x)
         elif snap is None:   # last block's residual add fused into ln_f (the summed stream itself is not needed)

@@ -247,12 +247,58 @@ def gelu(x):
     return F.gelu(x, approximate="tanh")
 
 
+# --------------------------------------------------------------------------------------- packed sequences
+def doc_bounds(doc_ids):
+    """``(doc_start, doc_end)`` of a packed batch: int32 ``[B, T]`` tensors holding, for every position
+    ``t``, the first and the last position of the document that contains it.  ``doc_ids`` is an integer
+    ``[B, T]`` tensor; a document begins at ``t = 0`` and wherever ``doc_ids[b, t] != doc_ids[b, t - 1]``
+    (the values themselves carry no meaning: an id that returns later in the row starts a new document).
+
+    Key ``k`` is visible to query ``q`` iff ``doc_start[b, q] <= k <= q``, and the position of ``t`` inside
+    its document is ``t - doc_start[b, t]``.  On the GPU this is one small kernel on the current stream with
+    no host read, so it can sit inside a captured step; on the CPU, the same values from torch ops.  The two
+    tensors are the halves of one contiguous ``[2, B, T]`` buffer."""
+    if doc_ids.dim() != 2 or doc_ids.is_floating_point() or doc_ids.dtype == torch.bool:
+        raise ValueError(f"doc_bounds: doc_ids must be an integer [B, T] tensor (got {tuple(doc_ids.shape)} "
+                         f"{doc_ids.dtype})")
+    B, T = doc_ids.shape
+    if _gpu(doc_ids):
+        out = torch.empty(2, B, T, device=doc_ids.device, dtype=torch.int32)
+        kernels().doc_bounds(_c(doc_ids.long()), out)
+        return out[0], out[1]
+    t = torch.arange(T, dtype=torch.int32).expand(B, T)
+    first = torch.ones(B, T, dtype=torch.bool)
+    first[:, 1:] = doc_ids[:, 1:] != doc_ids[:, :-1]
+    last = torch.ones(B, T, dtype=torch.bool)
+    last[:, :-1] = first[:, 1:]
+    start = torch.where(first, t, t.new_zeros(())).cummax(1).values
+    end = torch.where(last, t, t.new_full((), T - 1)).flip(1).cummin(1).values.flip(1)
+    out = torch.stack([start, end]).to(torch.int32)
+    return out[0], out[1]
+
+
+def doc_allowed(doc_start):
+    """bool ``[B, 1, T, T]`` (query, key): ``doc_start[b, q] <= k <= q``, the mask the kernels apply."""
+    T = doc_start.shape[1]
+    k = torch.arange(T, device=doc_start.device)
+    return ((k[None, None, :] <= k[None, :, None]) & (k[None, None, :] >= doc_start[:, :, None])).unsqueeze(1)
+
+
+def _check_bounds(doc_bounds, B, T, device, what):
+    ds, de = doc_bounds
+    for t in (ds, de):
+        if tuple(t.shape) != (B, T) or t.dtype != torch.int32 or t.device != device:
+            raise ValueError(f"{what}: doc_bounds must be the int32 [B, T] pair of ops.doc_bounds on the input's "
+                             f"device (got {tuple(t.shape)} {t.dtype} on {t.device})")
+    return _c(ds), _c(de)
+
+
 # --------------------------------------------------------------------------------------- attention
 class CausalAttentionFn(torch.autograd.Function):
     """qkv: [B, T, 3*H*64] (the c_attn output, read in place) -> y: [B, T, H*64]."""
 
     @staticmethod
-    def forward(ctx, qkv, n_head, snap=None, site=0, thr=0, ik=1.0):
+    def forward(ctx, qkv, n_head, snap=None, site=0, thr=0, ik=1.0, ds=None, de=None):
         qkv = _c(qkv)
         B, T, C3 = qkv.shape
         C = C3 // 3
@@ -260,7 +306,11 @@ class CausalAttentionFn(torch.autograd.Function):
         o = torch.empty(B, T, C, device=qkv.device, dtype=qkv.dtype)
         lse = torch.empty(B * n_head * T, device=qkv.device, dtype=torch.float32)
         scale = 1.0 / math.sqrt(C // n_head)
-        if snap is None:
+        ctx.doc = () if ds is None else (ds, de)    # not differentiable inputs: kept as plain attributes
+        if ds is not None:      # packed sequences: the DOC instantiations, with or without dropout
+            kernels().attn_fwd(q, k, v, o, lse, n_head, scale, snap, site, thr, ik, ds)
+            ctx.save_for_backward(qkv, o, lse, *(() if snap is None else (snap,)))
+        elif snap is None:
             kernels().attn_fwd(q, k, v, o, lse, n_head, scale)
             ctx.save_for_backward(qkv, o, lse)
         else:       # dropout on the probabilities, inside the flash kernels (the mask is never stored)
@@ -280,38 +330,59 @@ class CausalAttentionFn(torch.autograd.Function):
         sl = [slice(0, C), slice(C, 2 * C), slice(2 * C, 3 * C)]
         q, k, v = (qkv[:, :, s] for s in sl)
         dq, dk, dv = (dqkv[:, :, s] for s in sl)
-        if snap:
+        if ctx.doc:
+            kernels().attn_bwd(q, k, v, o, do, lse, Dd, dq, dk, dv, ctx.n_head, ctx.scale, snap[0] if snap else None,
+                               *ctx.drop, *ctx.doc)
+        elif snap:
             kernels().attn_bwd(q, k, v, o, do, lse, Dd, dq, dk, dv, ctx.n_head, ctx.scale, snap[0], *ctx.drop)
         else:
             kernels().attn_bwd(q, k, v, o, do, lse, Dd, dq, dk, dv, ctx.n_head, ctx.scale)
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
-def causal_attention(qkv, n_head: int, p: float = 0.0, rng_snapshot=None, site: int = 0):
+def causal_attention(qkv, n_head: int, p: float = 0.0, rng_snapshot=None, site: int = 0, doc_bounds=None):
     """Causal self-attention over the fused c_attn output.  ``p > 0`` drops attention probabilities
     (after the softmax) with the mask of ``(rng_snapshot, site)``; the probability realised is
     ``rng.effective_p(p, "attention")`` and the kept ones are scaled by its ``1 / keep``.  ``p == 0``
-    takes the path without dropout."""
+    takes the path without dropout.
+
+    ``doc_bounds`` (the pair of ``doc_bounds(doc_ids)``) packs several documents into a row: key ``k`` is
+    visible to query ``q`` iff ``doc_start[b, q] <= k <= q``.  The dropout mask stays the function of
+    ``(b, h, q, k)`` it is without documents.  ``None`` is the call as it was."""
+    B, T, C3 = qkv.shape
+    if doc_bounds is not None:
+        doc_bounds = _check_bounds(doc_bounds, B, T, qkv.device, "causal_attention")
     if _gpu(qkv):
         C = qkv.shape[-1] // 3
         if C // n_head != 64:
             raise NotImplementedError("flash attention kernel: head_dim 64")
         if p == 0.0:
-            return CausalAttentionFn.apply(qkv, n_head)
+            if doc_bounds is None:
+                return CausalAttentionFn.apply(qkv, n_head)
+            return CausalAttentionFn.apply(qkv, n_head, None, 0, 0, 1.0, *doc_bounds)
         thr, ik = _drop_args(p, rng_snapshot, "attention")
-        return CausalAttentionFn.apply(qkv, n_head, rng_snapshot, int(site), thr, ik)
-    B, T, C3 = qkv.shape
+        if doc_bounds is None:
+            return CausalAttentionFn.apply(qkv, n_head, rng_snapshot, int(site), thr, ik)
+        return CausalAttentionFn.apply(qkv, n_head, rng_snapshot, int(site), thr, ik, *doc_bounds)
     C = C3 // 3
     q, k, v = qkv.split(C, dim=2)
     q, k, v = (t.view(B, T, n_head, C // n_head).transpose(1, 2) for t in (q, k, v))
-    if p == 0.0:
+    if p == 0.0 and doc_bounds is None:
         y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+    elif p == 0.0:
+        y = F.scaled_dot_product_attention(q, k, v, attn_mask=doc_allowed(doc_bounds[0]))
     else:
-        _drop_args(p, rng_snapshot, "attention")
         s = (q @ k.transpose(-1, -2)) / math.sqrt(C // n_head)
-        s = s.masked_fill(torch.triu(torch.ones(T, T, dtype=torch.bool, device=qkv.device), 1), float("-inf"))
-        m = R.attention_mask(rng_snapshot, site, B, n_head, T, p)
-        y = (torch.softmax(s, -1) * (m.to(s.dtype) * R.inv_keep(p, "attention"))) @ v
+        if doc_bounds is None:
+            s = s.masked_fill(torch.triu(torch.ones(T, T, dtype=torch.bool, device=qkv.device), 1), float("-inf"))
+        else:
+            s = s.masked_fill(~doc_allowed(doc_bounds[0]), float("-inf"))
+        P = torch.softmax(s, -1)
+        if p != 0.0:
+            _drop_args(p, rng_snapshot, "attention")
+            m = R.attention_mask(rng_snapshot, site, B, n_head, T, p)
+            P = P * (m.to(s.dtype) * R.inv_keep(p, "attention"))
+        y = P @ v
     return y.transpose(1, 2).reshape(B, T, C)
 
 
@@ -335,12 +406,16 @@ class EmbeddingFn(torch.autograd.Function):
     paths (the LM head's backward runs first and leaves its dw in the pairing slot)."""
 
     @staticmethod
-    def forward(ctx, idx, wte, wpe, snap=None, site=0, thr=0, ik=1.0):
+    def forward(ctx, idx, wte, wpe, snap=None, site=0, thr=0, ik=1.0, ds=None, de=None):
         B, T = idx.shape
         C = wte.shape[1]
         idx = _c(idx.long())
         out = torch.empty(B, T, C, device=wte.device, dtype=wte.dtype)
-        if snap is None:
+        ctx.doc_end = de
+        if ds is not None:      # packed sequences: the position restarts at every document start
+            kernels().embed_fwd(idx, wte, wpe, out, T, snap, site, thr, ik, ds)
+            ctx.save_for_backward(idx, *(() if snap is None else (snap,)))
+        elif snap is None:
             kernels().embed_fwd(idx, wte, wpe, out, T)
             ctx.save_for_backward(idx)
         else:       # embedding dropout: mask and scale applied while writing
@@ -369,23 +444,38 @@ class EmbeddingFn(torch.autograd.Function):
         if T < wpe_shape[0]:
             dwpe[T:].zero_()                       # rows past the sequence get no gradient
         acc, touched = _emb_scratch(dx.device, wte_shape[0], wte_shape[1])
-        if snap:    # the forward's mask and scale are applied while dX is read
+        if ctx.doc_end is not None:     # dwpe by position inside the document, in a fixed order of summation
+            kernels().embed_bwd(_c(dx), idx, dwte, dwpe, acc, touched, T, False, snap[0] if snap else None,
+                                *ctx.drop, ctx.doc_end)
+        elif snap:    # the forward's mask and scale are applied while dX is read
             kernels().embed_bwd(_c(dx), idx, dwte, dwpe, acc, touched, T, False, snap[0], *ctx.drop)
         else:
             kernels().embed_bwd(_c(dx), idx, dwte, dwpe, acc, touched, T, False)
-        return None, ret_wte, dwpe, None, None, None, None
+        return None, ret_wte, dwpe, None, None, None, None, None, None
 
 
-def embedding(idx, wte, wpe, p: float = 0.0, rng_snapshot=None, site: int = 0):
+def embedding(idx, wte, wpe, p: float = 0.0, rng_snapshot=None, site: int = 0, doc_bounds=None):
     """Token + position embedding; ``p > 0`` applies embedding dropout with the mask of
-    ``(rng_snapshot, site)`` inside the kernels (forward while writing, backward while reading dX)."""
+    ``(rng_snapshot, site)`` inside the kernels (forward while writing, backward while reading dX).
+    With ``doc_bounds`` (packed sequences) row ``(b, t)`` takes ``wpe[t - doc_start[b, t]]``; the dropout
+    mask stays indexed by ``(b, t)``."""
+    if doc_bounds is not None:
+        doc_bounds = _check_bounds(doc_bounds, idx.shape[0], idx.shape[1], wte.device, "embedding")
     if _gpu(wte):
         if p == 0.0:
-            return EmbeddingFn.apply(idx, wte, wpe)
+            if doc_bounds is None:
+                return EmbeddingFn.apply(idx, wte, wpe)
+            return EmbeddingFn.apply(idx, wte, wpe, None, 0, 0, 1.0, *doc_bounds)
         thr, ik = _drop_args(p, rng_snapshot, "elementwise")
-        return EmbeddingFn.apply(idx, wte, wpe, rng_snapshot, int(site), thr, ik)
+        if doc_bounds is None:
+            return EmbeddingFn.apply(idx, wte, wpe, rng_snapshot, int(site), thr, ik)
+        return EmbeddingFn.apply(idx, wte, wpe, rng_snapshot, int(site), thr, ik, *doc_bounds)
     T = idx.shape[1]
-    out = F.embedding(idx, wte) + wpe[:T].unsqueeze(0)
+    if doc_bounds is None:
+        out = F.embedding(idx, wte) + wpe[:T].unsqueeze(0)
+    else:
+        pos = torch.arange(T, device=idx.device)[None, :] - doc_bounds[0].long()
+        out = F.embedding(idx, wte) + F.embedding(pos, wpe)
     return out if p == 0.0 else _cpu_drop(out, p, rng_snapshot, site)
 
 
