@@ -13,11 +13,21 @@
 //    (4 k-steps per read), the B operand (conv1 output im2col) by conflict-free ds_read_b32: 4x4-pixel
 //    output tiles with a channel stride of 144 floats (== 16 mod 32 banks) put the two K-lane groups
 //    of each 32-lane half on disjoint bank sets;
+//    with conv1 on the VALU (the default) the weight slice goes through registers instead: every global
+//    load of the block, the four conv2 biases included, is one inline-asm batch at the block start
+//    (16 loads, hidden from hipcc's vmcnt bookkeeping), retired by one vmcnt(0) after conv1;
+//  * the conv2 operand reads run 10 k-steps (B) / two quads (A) ahead of their MFMAs in a register
+//    ring, every k-step fenced, so the MFMA chain waits for no LDS round trip after its first;
 //  * bias + ReLU + 2x2 max-pool (first maximum in scan order, as ATen) on the accumulator registers with
-//    lane shuffles (pixel neighbours are lanes ^1 / ^4 / ^5 of a 4x4 tile);
+//    lane shuffles (pixel neighbours are lanes ^1 / ^4 / ^5 of a 4x4 tile): the twelve exchanges of the
+//    four accumulator rows as one round, then the compares, then one batch of stores, with no vmcnt
+//    wait between the last MFMA and the end of the kernel;
 //  * P1 / A1 (conv1 pooled output + argmax codes, kept for backward) are written from LDS right after
-//    the conv1 -> conv2 barrier (split between the two co-half blocks): behind the LDS-DMA wait, so no
-//    store delays it, and they drain under conv2 instead of at the kernel tail.
+//    the conv1 -> conv2 barrier (split between the two co-half blocks), behind the ring's opening
+//    reads: they drain under conv2 instead of at the kernel tail.
+// What to look for in `tools/isa_load_order.py csrc/kernels/lenet_v2.hip k_conv_fwd2 --lds` (the
+// measurements are in profiles/conv_fwd_waits/): `16L w13` at the entry, no `L` up to the second
+// `BAR`, no `g<n>` below 4 inside the 125-MFMA block before its last 8 MFMAs, no `w<n>` after it.
 //
 // Packed conv2 weight ("Wp"), written by the optimizer's repack epilogue (optim.hip, pack mode 2):
 //   Wp[ct][cotile][kq][co16][132]  (ct = co >> 5, cotile = (co >> 4) & 1, co16 = co & 15)
@@ -67,6 +77,10 @@ __global__ __launch_bounds__(512) void k_conv_fwd2(const float* __restrict__ Xb,
   __shared__ __attribute__((aligned(16))) float smem[kL_TOT];
   const int b = blockIdx.x, ct = blockIdx.y, t = threadIdx.x, l = t & 63, w = t >> 6;
   PMARK(0);
+  // the output pointers are wanted in SGPRs from here on: left to itself hipcc fetches each from the
+  // kernel arguments inside the branch that stores through it, and that scalar load's lgkmcnt(0)
+  // (scalar loads return out of order) drains every LDS read in flight at that point
+  asm volatile("" ::"s"(P1), "s"(A1), "s"(P2), "s"(A2));
   // ---- phase 0: register loads first (image, conv1 weights, this wave's conv2 biases) ----
   const int cotile = w >> 2, pxt = w & 3, kq = l >> 4, j = l & 15;
   const int co_base = ct * 32 + cotile * 16 + kq * 4;          // + r: the accumulator row's channel
@@ -75,10 +89,11 @@ __global__ __launch_bounds__(512) void k_conv_fwd2(const float* __restrict__ Xb,
   float bias2[4];
   float4 wr[9];
   if constexpr (conv1_valu) {
-    // EVERY global load before conv1 is inline asm, the conv2 weight image (9 x 16 B per lane) issued
-    // right behind the image and conv1 weights, so the weights are in flight from the block start;
-    // hipcc never sees these loads, so none of its vmcnt waits can drain the weights early -- the
-    // first three are retired by the explicit vmcnt(9), the weights by a vmcnt(0) after conv1
+    // EVERY global load of the block is inline asm and issued here: the conv2 weight image (9 x 16 B
+    // per lane) right behind the image and conv1 weights, then this lane's four conv2 biases, so all
+    // of them are in flight from the block start; hipcc never sees these loads, so none of its vmcnt
+    // waits can drain them early (and none of its waits counts them later) -- the first three are
+    // retired by the explicit vmcnt(13), weights and biases together by a vmcnt(0) after conv1
     const float* xsrc = Xb + (size_t)b * kImg + 4 * min(t, kImg / 4 - 1);
     const float* w1src = w1 + 4 * min(t, 124);
     const float* b1src = b1 + min(t, 19);
@@ -89,7 +104,10 @@ __global__ __launch_bounds__(512) void k_conv_fwd2(const float* __restrict__ Xb,
 #pragma unroll
     for (int i = 0; i < 9; ++i)
       asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wr[i]) : "v"(wsrc + i * 8 * 256) : "memory");
-    asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      asm volatile("global_load_dword %0, %1, off" : "=v"(bias2[r]) : "v"(b2 + min(co_base + r, 49)) : "memory");
+    asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
   } else {
     xv = reinterpret_cast<const float4*>(Xb + (size_t)b * kImg)[min(t, kImg / 4 - 1)];
     wv = reinterpret_cast<const float4*>(w1)[min(t, 124)];
@@ -243,69 +261,115 @@ __global__ __launch_bounds__(512) void k_conv_fwd2(const float* __restrict__ Xb,
   }
   }   // conv1_valu
   if constexpr (conv1_valu) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // retires the conv2 weights and the conv2 biases (issued in the opening batch); the biases are
+    // tied to the wait so that no use of them can be scheduled above it
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(bias2[0]), "+v"(bias2[1]), "+v"(bias2[2]), "+v"(bias2[3])
+                 :
+                 : "memory");
 #pragma unroll
     for (int i = 0; i < 9; ++i) *reinterpret_cast<float4*>(smem + kL_W + (w + 8 * i) * 256 + l * 4) = wr[i];
-    // the conv2 biases are needed only by the epilogue: loaded now, they land under conv2
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bias2[r] = b2[min(co_base + r, 49)];
   }
   PMARK(2);
-  // conv1 output visible + this wave's LDS-DMA landed, then every wave's (barrier)
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  // conv1 output and conv2 weights visible (LDS writes only: no global load is outstanding here);
+  // the LDS-DMA form also waits for this wave's DMA to land.  Then every wave's (barrier)
+  if constexpr (conv1_valu)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  else
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   PMARK(3);
-  // ---- P1 / A1 for backward (this block's 10 channels): issued now, they drain under conv2 ----
-  if (t < 360) {
-    const int c0 = ct * 10 * 144;
-    // non-temporal: read again only by the conv backward three kernels later, so these 1.8 MB are
-    // streamed out instead of sitting dirty in the XCD L2s for the end-of-kernel write-back
-    typedef float nt_f4 __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(reinterpret_cast<const nt_f4*>(smem + kL_XS + c0)[t],
-                                reinterpret_cast<nt_f4*>(P1 + (size_t)b * kP1 + c0) + t);
-    __builtin_nontemporal_store(
-        reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(smem + kL_CODE) + c0)[t],
-        reinterpret_cast<uint32_t*>(A1 + (size_t)b * kP1 + c0) + t);
-  }
   // ---- phase 2: conv2 (20->50, 5x5): wave = (co tile of 16, 4x4 pixel tile), K = 500 ----
+  // One accumulator, k-steps ascending (the sum of every output is the same fmaf chain whatever the
+  // read schedule).  The operand reads run ahead of the MFMAs in a register ring: the B value of
+  // k-step s + kBD is issued in front of MFMA s, the A quad (4 k-steps per ds_read_b128) two quads
+  // ahead, so no MFMA waits for an LDS round trip after the first; every k-step is fenced
+  // (sched_barrier) so that the order below is the order issued, and the compiler's counted lgkmcnt
+  // waits (LDS returns in order) leave kBD reads in flight.  All indices are compile-time: the ring
+  // is the live range of bq[] / aq[], about kBD + 12 registers.
+  constexpr int kBD = 10;
   const int oh = (pxt >> 1) * 4 + (j >> 2), ow = (pxt & 1) * 4 + (j & 3);
   f32x4 acc = {0.f};
   {
     const float* wa = smem + kL_W + ((cotile * 4 + kq) * 16 + j) * kRowS;   // A: W[co = j][k-steps], b128 reads
     const float* xb = smem + kL_XS + kq * 144 + oh * 12 + ow;             // B: im2col[k][px]
+    auto bread = [&](int s) -> float {                                      // s compile-time after unrolling
+      const int tap = s / 5, kh = tap / 5, kw = tap % 5, cib = 4 * (s % 5);
+      return xb[cib * 144 + kh * 12 + kw];
+    };
+    // P1 / A1 for backward (this block's 10 channels): their LDS reads go first, the stores behind
+    // the ring's opening reads, so neither waits for the other; they drain under conv2.  Non-temporal:
+    // read again only by the conv backward three kernels later, so these 1.8 MB are streamed out
+    // instead of sitting dirty in the XCD L2s for the end-of-kernel write-back
+    typedef float nt_f4 __attribute__((ext_vector_type(4)));
+    const int c0 = ct * 10 * 144, tp = min(t, 359);
+    const nt_f4 p1v = reinterpret_cast<const nt_f4*>(smem + kL_XS + c0)[tp];
+    const uint32_t a1v = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(smem + kL_CODE) + c0)[tp];
+    __builtin_amdgcn_sched_barrier(0);
+    float4 aq[32];
+    float bq[125];
+    aq[0] = *reinterpret_cast<const float4*>(wa);
 #pragma unroll
-    for (int u = 0; u < 32; ++u) {
-      const float4 a4 = *reinterpret_cast<const float4*>(wa + 4 * u);
+    for (int s = 0; s < kBD; ++s) bq[s] = bread(s);
+    aq[1] = *reinterpret_cast<const float4*>(wa + 4);
+    __builtin_amdgcn_sched_barrier(0);
+    if (t < 360) {
+      __builtin_nontemporal_store(p1v, reinterpret_cast<nt_f4*>(P1 + (size_t)b * kP1 + c0) + t);
+      __builtin_nontemporal_store(a1v, reinterpret_cast<uint32_t*>(A1 + (size_t)b * kP1 + c0) + t);
+    }
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int s = 4 * u + e;
-        if (s < 125) {
-          const int tap = s / 5, kh = tap / 5, kw = tap % 5, cib = 4 * (s % 5);
-          const float bv = xb[cib * 144 + kh * 12 + kw];
-          acc = mfma16x16x4(e == 0 ? a4.x : e == 1 ? a4.y : e == 2 ? a4.z : a4.w, bv, acc);
-        }
-      }
+    for (int s = 0; s < 125; ++s) {
+      const int u = s >> 2, e = s & 3;
+      if (e == 0 && u + 2 < 32) aq[u + 2] = *reinterpret_cast<const float4*>(wa + 4 * (u + 2));
+      if (s + kBD < 125) bq[s + kBD] = bread(s + kBD);
+      const float4 a4 = aq[u];
+      acc = mfma16x16x4(e == 0 ? a4.x : e == 1 ? a4.y : e == 2 ? a4.z : a4.w, bq[s], acc);
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
   PMARK(4);
   // ---- epilogue: bias + ReLU + 2x2 max-pool across lanes (^1 = dx, ^4 = dy), P2 / A2 ----
+  // All four rows at once: twelve lane exchanges issued back to back (one round trip, not four),
+  // then the four compare chains, then the stores in one batch.  The biases arrived with the opening
+  // loads, so no vmcnt wait stands between the last MFMA and the end of the kernel: the P1 / A1
+  // stores keep draining under the epilogue.
   {
     const bool anchor = (j & 5) == 0;                  // top-left pixel of a pooling window
     const int ph = oh >> 1, pw = ow >> 1;
+    float v[4], v1[4], v4[4], v5[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = fmaxf(acc[r] + bias2[r], 0.f);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float v = fmaxf(acc[r] + bias2[r], 0.f);
-      const float v1 = __shfl_xor(v, 1, 64), v4 = __shfl_xor(v, 4, 64), v5 = __shfl_xor(v, 5, 64);
-      float best = v;
-      int code = 0;
-      if (v1 > best) { best = v1; code = 1; }
-      if (v4 > best) { best = v4; code = 2; }
-      if (v5 > best) { best = v5; code = 3; }
-      const int co = co_base + r;
-      if (anchor && co < 50) {
-        const size_t o = (size_t)b * kFeat + co * 16 + ph * 4 + pw;
-        P2[o] = best;
-        A2[o] = (uint8_t)code;
+      v1[r] = __shfl_xor(v[r], 1, 64);
+      v4[r] = __shfl_xor(v[r], 4, 64);
+      v5[r] = __shfl_xor(v[r], 5, 64);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    float best[4];
+    int code[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {                      // first maximum in scan order (ATen): strict >
+      best[r] = v[r];
+      code[r] = 0;
+      if (v1[r] > best[r]) { best[r] = v1[r]; code[r] = 1; }
+      if (v4[r] > best[r]) { best[r] = v4[r]; code[r] = 2; }
+      if (v5[r] > best[r]) { best[r] = v5[r]; code[r] = 3; }
+    }
+    // co_base is a multiple of 4 and 50 = 48 + 2: rows 0 / 1 of a quad are real iff co_base < 50,
+    // rows 2 / 3 iff co_base + 2 < 50
+    if (anchor && co_base < 50) {
+      const size_t o = (size_t)b * kFeat + co_base * 16 + ph * 4 + pw;
+      P2[o] = best[0];
+      P2[o + 16] = best[1];
+      A2[o] = (uint8_t)code[0];
+      A2[o + 16] = (uint8_t)code[1];
+      if (co_base + 2 < 50) {
+        P2[o + 32] = best[2];
+        P2[o + 48] = best[3];
+        A2[o + 32] = (uint8_t)code[2];
+        A2[o + 48] = (uint8_t)code[3];
       }
     }
   }

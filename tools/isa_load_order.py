@@ -9,13 +9,17 @@ and, for every kernel whose name contains one of the given substrings, prints
 * the run-length-encoded sequence of global loads (``L``), stores (``S``), atomics (``A``),
   ``s_waitcnt vmcnt(n)`` (``w<n>``), MFMAs (``M``), barriers (``BAR``) and conditional branches
   (``br``), one line per basic block that holds any of them (blocks with nothing but branches
-  are left out unless ``--all-blocks`` is given).
+  are left out unless ``--all-blocks`` is given).  With ``--lds`` the LDS side is listed too:
+  ``ds_read*`` (``r``), ``ds_write*`` (``d``), lane exchanges -- ``ds_bpermute`` / ``ds_permute`` /
+  ``ds_swizzle`` and DPP moves -- (``x``) and ``s_waitcnt lgkmcnt(n)`` (``g<n>``; a wait on both
+  counters prints ``w<n> g<m>``).
 
 A kernel that issues all its loads before the first MFMA shows ``26L`` ahead of the first ``M``;
 one that the compiler serialised shows ``4L w0 8M 4L w0 ...``.
 
     python tools/isa_load_order.py csrc/kernels/lenet.hip k_fc1_fwd k_fc_bwd
     python tools/isa_load_order.py csrc/kernels/optim.hip k_adam k_sgd --out profiles/x.txt
+    python tools/isa_load_order.py csrc/kernels/lenet_v2.hip k_conv_fwd2 --lds
 """
 import argparse
 import os
@@ -29,6 +33,9 @@ ARCH = "gfx950"
 
 _TOKEN = re.compile(
     r"^\s*(global_load\w*|buffer_load\w*|\w*_store\w*|\w*_atomic\w*|s_waitcnt|v_mfma\w*|s_barrier|s_cbranch\w*)\b(.*)$")
+_TOKEN_LDS = re.compile(
+    r"^\s*(global_load\w*|buffer_load\w*|\w*_store\w*|\w*_atomic\w*|s_waitcnt|v_mfma\w*|s_barrier|s_cbranch\w*"
+    r"|ds_\w+|v_\w+_dpp)\b(.*)$")
 _LABEL = re.compile(r"^([.\w$]+):")
 _REMARK = re.compile(r"remark:\s+(.+?): (\S+)(?: \[-Rpass[^\]]*\])?\s*$")
 _KEYS = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]",
@@ -81,6 +88,31 @@ def resources(remarks):
     return res
 
 
+def classify_lds(op, rest):
+    """Tokens of one instruction with --lds: the plain token (if any) and the LDS-side ones."""
+    if op == "s_waitcnt":
+        toks = []
+        m = re.search(r"vmcnt\((\d+)\)", rest)
+        if m:
+            toks.append(f"w{m.group(1)}")
+        m = re.search(r"lgkmcnt\((\d+)\)", rest)
+        if m:
+            toks.append(f"g{m.group(1)}")
+        return toks
+    if op.endswith("_dpp"):
+        return ["x"]
+    if op.startswith("ds_"):
+        if re.match(r"ds_(bpermute|permute|swizzle)", op):
+            return ["x"]
+        if re.match(r"ds_(read|load)", op):
+            return ["r"]
+        if re.match(r"ds_(write|store)", op):
+            return ["d"]
+        return []                                    # LDS atomics, ds_nop, gws: not listed
+    t = classify(op, rest)
+    return [t] if t else []
+
+
 def classify(op, rest):
     if op == "s_waitcnt":
         m = re.search(r"vmcnt\((\d+)\)", rest)
@@ -122,12 +154,12 @@ def rle(tokens):
         while j < len(tokens) and tokens[j] == tokens[i]:
             j += 1
         n = j - i
-        out.append(f"{n}{tokens[i]}" if n > 1 or tokens[i] in ("L", "S", "M", "A") else tokens[i])
+        out.append(f"{n}{tokens[i]}" if n > 1 or tokens[i] in ("L", "S", "M", "A", "r", "d", "x") else tokens[i])
         i = j
     return " ".join(out)
 
 
-def order(lines, all_blocks=False):
+def order(lines, all_blocks=False, lds=False):
     """[(block label, rle string)] for the basic blocks that hold any matched instruction."""
     blocks, label, toks = [], "entry", []
 
@@ -141,17 +173,20 @@ def order(lines, all_blocks=False):
                 blocks.append((label, rle(toks)))
             label, toks = m.group(1), []
             continue
-        m = _TOKEN.match(line)
+        m = (_TOKEN_LDS if lds else _TOKEN).match(line)
         if m:
-            t = classify(m.group(1), m.group(2))
-            if t:
-                toks.append(t)
+            if lds:
+                toks.extend(classify_lds(m.group(1), m.group(2)))
+            else:
+                t = classify(m.group(1), m.group(2))
+                if t:
+                    toks.append(t)
     if keep(toks):
         blocks.append((label, rle(toks)))
     return blocks
 
 
-def report(src, wanted, extra=(), all_blocks=False):
+def report(src, wanted, extra=(), all_blocks=False, lds=False):
     asm, remarks = compile_to_asm(src, file_flags(src) + list(extra))
     res = resources(remarks)
     bodies = kernel_bodies(asm)
@@ -163,7 +198,7 @@ def report(src, wanted, extra=(), all_blocks=False):
             continue
         out.append(f"== {pretty[n]}")
         out.append("   " + "  ".join(f"{k.split(' [')[0]}={res[n].get(k, '?')}" for k in _KEYS))
-        for label, seq in order(bodies[n], all_blocks):
+        for label, seq in order(bodies[n], all_blocks, lds):
             out.append(f"   {label:>10}: {seq}")
         out.append("")
     if not out:
@@ -178,9 +213,11 @@ def main(argv=None):
     ap.add_argument("--out", help="also write the report to this file")
     ap.add_argument("-X", dest="extra", action="append", default=[], help="extra compiler flag")
     ap.add_argument("--all-blocks", action="store_true", help="also list blocks that hold only branches")
+    ap.add_argument("--lds", action="store_true",
+                    help="also list LDS reads (r), writes (d), lane exchanges (x) and lgkmcnt waits (g<n>)")
     ap.add_argument("-q", "--quiet", action="store_true", help="with --out: do not print the report")
     a = ap.parse_args(argv)
-    text = report(a.source, a.kernels, a.extra, a.all_blocks)
+    text = report(a.source, a.kernels, a.extra, a.all_blocks, a.lds)
     if not (a.quiet and a.out):
         print(text)
     if a.out:
