@@ -54,6 +54,10 @@ hipError_t pde_sgd_flat(float* p, float* g, float* buf, long long n, float lr, f
                         int fold_stride, int pack_mode, long long fold2_off, int fold2_len, int fold2_nrep,
                         int fold2_stride, const float* lr_tab, int lr_len, hipStream_t st);
 hipError_t pde_lenet_pack_w2(const float* w2, float* dst, hipStream_t st);
+// pde_adam_flat without peer_dev runs the lean kernel (no all-reduce code compiled in); on != 0 makes such
+// calls take the general kernel (the one of the fused all-reduce routes, with no side blocks) instead.
+// Process-wide, read at every launch: for tests that compare the two within one process.
+void pde_optim_force_general(int on);
 
 // ---- LeNet step v2: csrc/kernels/lenet_v2.hip ----
 hipError_t pde_lenet_conv_fwd2(const float* Xb, int B, const float* w1, const float* b1, const float* Wp,

@@ -11,6 +11,16 @@
 // lr_tab (nullable): a device table of per-step learning rates, step t uses lr_tab[min(t-1, lr_len-1)]
 // (pde_lr.h), so a captured launch follows a schedule; null = the by-value lr.
 // grad_scale folds the DDP 1/world_size average (or any loss scale) into the update.
+// Two Adam kernels are compiled, k_adam<PROF, NTP, AR>:
+//   AR = false, the lean kernel: every call without a peer (the single-GPU LeNet step, GPT-2, ResNet-18).
+//     Its one argument is the Lean struct, which carries what the host worked out to size the grid
+//     (holes, compressed length, block counts per role, 1-b1, 1-b2): no peer code, no pass loop, no
+//     64-bit division.  Fold blocks have the lowest block ids (the longest chain starts first); a
+//     block fetches its arguments in one batch, issues the scalar load of *step and its first
+//     iteration's vector loads, and only then waits for the step and does the lr-table lookup and
+//     the bias-correction powf / sqrt / divide, under the loads.  k_sgd has the same shape.
+//   AR = true, the general kernel: the fused all-reduce below (side blocks first, two passes); also
+//     what pde_optim_force_general selects for a peer-less call, so tests can compare the two.
 // Optional fused all-reduce (Adam only, the W > 1 "fused" LeNet schedule): the first ar_nvb blocks
 // all-reduce the flat range [ar_lo4, n4) (the conv-gradient bucket) across ranks with the xGMI peer
 // protocol while the other blocks update [0, ar_lo4); those blocks then wait for the reduction (the
@@ -28,6 +38,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -55,6 +66,11 @@ struct Fold {      // up to two replicated gradient ranges (LeNet: conv1 atomic 
 // each, with a vmcnt(0) between most of them (tools/isa_load_order.py); making them unconditional
 // on clamped addresses puts them in one batch but did not shorten the fold blocks
 // (profiles/lenet_load_order/rejected_adam_fold_batch/).
+// The general Adam kernel appends the fold blocks (highest block ids) and derives holes, block counts
+// and lane addresses on the device (make_holes, fold_blocks, fold_elem, fold_lane).  The lean Adam
+// kernel and k_sgd put the fold blocks first and take all of that from the host in the Lean struct
+// (lean_fold_addr / lean_fold_load / lean_fold_sum: the same loads and the same order of additions,
+// all issued before the wait for the step counter).
 constexpr int kMaxFold = 16;
 constexpr int kLS = 4;
 
@@ -184,14 +200,15 @@ __device__ __forceinline__ void wait_epoch(const long long* epoch, long long t, 
   __syncthreads();
 }
 
-template <bool PROF, bool NTP>
-__global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, float* __restrict__ g,
+template <bool PROF, bool NTP, bool AR>
+__global__ __launch_bounds__(256) std::enable_if_t<AR> k_adam(float* __restrict__ p, float* __restrict__ g,
                                               float* __restrict__ m, float* __restrict__ v, long long n4,
                                               float lr, float b1, float b2, float eps, float wd, int decoupled,
                                               float grad_scale, long long* __restrict__ step,
                                               unsigned* __restrict__ arrive, int bump, Pack pk, Fold fd, FusedAR ar,
                                               unsigned long long* __restrict__ prof,
                                               const float* __restrict__ lr_tab, int lr_len) {
+  // AR = true: the general kernel (fused all-reduce side blocks, two passes), the W > 1 adam1 / adam2 routes
   if constexpr (PROF) {
     if (threadIdx.x == 0) prof[(size_t)blockIdx.x * 8] = __builtin_amdgcn_s_memrealtime();
   }
@@ -289,11 +306,192 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, float* __re
   }
 }
 
+// ---- the lean kernels: every call without a fused all-reduce (k_adam<.,.,false>) and every k_sgd ----
+// One by-value struct: everything the host already worked out to size the grid (holes, compressed
+// length, block counts per role, 1-b1, 1-b2) travels as an argument, so a block fetches its
+// arguments in one batch and does no 64-bit division.
+struct Lean {
+  float* p; float* g; float* m; float* v;   // SGD: m = momentum buffer, v unused
+  long long* step;
+  unsigned* arrive;
+  const float* lr_tab;
+  unsigned long long* prof;
+  float* pack_dst;
+  long long pack_off;        // -1 = no repack
+  Holes holes;
+  long long n4c;             // compressed float4 count (replica sets skipped)
+  long long f_off[2];        // fold ranges in block order (range 0's blocks first); see Fold1
+  int f_len[2], f_nrep[2], f_s4[2];   // f_s4 = stride / 4
+  int nfb0, nfb;             // fold blocks of range 0, of both ranges; 0 = no fold
+  int nmain;                 // main (grid-stride) blocks
+  int pack_mode, bump, lr_len, flag;   // flag: Adam decoupled / SGD nesterov
+  float lr, grad_scale, wd;
+  float a, b, oma, omb, eps;   // Adam: b1, b2, 1-b1, 1-b2, eps; SGD: momentum, dampening
+};
+
+// Block ids: fold blocks first (their chain is the longest: seven loads, two shuffle rounds, scattered
+// 4-byte stores and the Wp index arithmetic), then the main blocks.
+struct LeanFold {
+  long long e;      // flat element this lane updates (-1: none)
+  int nrep;         // replicas this lane's float4 has (1 past len)
+  int lane;
+  const float4* g4; // replica 0 of this lane's float4
+  long long s4;
+};
+
+__device__ __forceinline__ LeanFold lean_fold_addr(const Lean& a, const long long (&f_off)[2], int fb) {
+  const int k = fb < a.nfb0 ? 0 : 1;
+  const int j = (int)(((unsigned)(k ? fb - a.nfb0 : fb) * 256u + threadIdx.x) / kLS);   // float4 in the slot
+  const int lane = threadIdx.x % kLS;
+  const int s4 = a.f_s4[k];
+  const bool valid = j < s4;
+  LeanFold f;
+  f.e = valid ? f_off[k] + 4 * j + lane : -1;
+  f.nrep = (valid && 4 * j < a.f_len[k]) ? a.f_nrep[k] : (valid ? 1 : 0);
+  f.lane = lane;
+  f.g4 = reinterpret_cast<const float4*>(a.g + f_off[k]) + (valid ? j : 0);   // f_off % 4 == 0
+  f.s4 = s4;
+  return f;
+}
+
+// the replica loads of fold_lane, and its sum (same order of additions)
+__device__ __forceinline__ void lean_fold_load(const LeanFold& f, float4 (&x)[kMaxFold / kLS]) {
+#pragma unroll
+  for (int q = 0; q < kMaxFold / kLS; ++q) {
+    const int r = f.lane + q * kLS;
+    x[q] = r < f.nrep ? f.g4[(long long)r * f.s4] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+__device__ __forceinline__ float lean_fold_sum(const LeanFold& f, const float4 (&x)[kMaxFold / kLS]) {
+  float4 a = x[0];
+#pragma unroll
+  for (int q = 1; q < kMaxFold / kLS; ++q) { a.x += x[q].x; a.y += x[q].y; a.z += x[q].z; a.w += x[q].w; }
+#pragma unroll
+  for (int o = 1; o < kLS; o <<= 1) {
+    a.x += __shfl_xor(a.x, o); a.y += __shfl_xor(a.y, o); a.z += __shfl_xor(a.z, o); a.w += __shfl_xor(a.w, o);
+  }
+  return f.lane == 0 ? a.x : f.lane == 1 ? a.y : f.lane == 2 ? a.z : a.w;
+}
+
+struct AdamStep {   // per-launch constants that need the step counter
+  float lr, step_size, bc2s;
+};
+
+__device__ __forceinline__ AdamStep adam_step(const Lean& a, long long t) {
+  AdamStep c;
+  c.lr = sched_lr(a.lr, a.lr_tab, a.lr_len, t);
+  const float bc1 = 1.f - powf(a.a, (float)t);
+  const float bc2 = 1.f - powf(a.b, (float)t);
+  c.step_size = c.lr / bc1;
+  c.bc2s = sqrtf(bc2);
+  return c;
+}
+
+template <bool NTP>
+__device__ __forceinline__ void adam_f4(const Lean& a, const AdamStep& c, long long i, float4 pp, float4 gg,
+                                        float4 mm, float4 vv) {
+  const Pack pk{a.pack_off, a.pack_dst, a.pack_mode};
+  float4* p4 = reinterpret_cast<float4*>(a.p);
+  float4* m4 = reinterpret_cast<float4*>(a.m);
+  float4* v4 = reinterpret_cast<float4*>(a.v);
+  float* pa = &pp.x; float* ga = &gg.x; float* ma = &mm.x; float* va = &vv.x;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    adam_elem<1>(pa[j], ma[j], va[j], ga[j] * a.grad_scale, c.lr, a.wd, a.flag, a.oma, a.omb, a.b, c.step_size,
+                 c.bc2s, a.eps);
+    pack_store(pk, 4 * i + j, pa[j]);
+  }
+  // moments non-temporal, NTP: the parameters too (see the general kernel)
+  typedef float nt_f4 __attribute__((ext_vector_type(4)));
+  if constexpr (NTP) __builtin_nontemporal_store(*reinterpret_cast<nt_f4*>(&pp), reinterpret_cast<nt_f4*>(p4 + i));
+  else p4[i] = pp;
+  __builtin_nontemporal_store(*reinterpret_cast<nt_f4*>(&mm), reinterpret_cast<nt_f4*>(m4 + i));
+  __builtin_nontemporal_store(*reinterpret_cast<nt_f4*>(&vv), reinterpret_cast<nt_f4*>(v4 + i));
+}
+
+// AR = false: no fused all-reduce, one pass.  Order of a block: arguments (one wait); the scalar
+// load of *step issued; the first iteration's vector loads issued (a fold block: p / m / v and its
+// replicas); only then the wait for the step, the lr table and the bias-correction powf / sqrt /
+// divide, all under the vector loads; update and stores.  The sched_barriers pin that order.
+template <bool PROF, bool NTP, bool AR>
+__global__ __launch_bounds__(256) std::enable_if_t<!AR> k_adam(const Lean a) {
+  if constexpr (PROF) {
+    if (threadIdx.x == 0) a.prof[(size_t)blockIdx.x * 8] = __builtin_amdgcn_s_memrealtime();
+  }
+  const long long s0 = *a.step;
+  long long f_off[2] = {a.f_off[0], a.f_off[1]};
+  asm("" : "+s"(f_off[0]), "+s"(f_off[1]));            // fetched with the other arguments, not on the fold path
+  __builtin_amdgcn_sched_barrier(0);
+  long long t;
+  if ((int)blockIdx.x < a.nfb) {                       // fold block
+    const LeanFold f = lean_fold_addr(a, f_off, blockIdx.x);
+    float pa = 0.f, ma = 0.f, va = 0.f;
+    if (f.e >= 0) {
+      pa = a.p[f.e];
+      ma = a.m[f.e];
+      va = a.v[f.e];
+    }
+    float4 x[kMaxFold / kLS];
+    lean_fold_load(f, x);
+    __builtin_amdgcn_sched_barrier(0);
+    t = a.bump < 0 ? s0 : s0 + 1;                      // bump < 0: counter pre-advanced by an earlier kernel
+    const AdamStep c = adam_step(a, t);
+    const float gf = lean_fold_sum(f, x);
+    if (f.e >= 0) {
+      adam_elem<2>(pa, ma, va, gf * a.grad_scale, c.lr, a.wd, a.flag, a.oma, a.omb, a.b, c.step_size, c.bc2s, a.eps);
+      if constexpr (NTP) {
+        __builtin_nontemporal_store(pa, a.p + f.e);
+        __builtin_nontemporal_store(ma, a.m + f.e);
+        __builtin_nontemporal_store(va, a.v + f.e);
+        __builtin_nontemporal_store(gf, a.g + f.e);    // p.grad holds the true (folded) gradient
+      } else {
+        a.p[f.e] = pa; a.m[f.e] = ma; a.v[f.e] = va;
+        a.g[f.e] = gf;                                 // p.grad holds the true (folded) gradient
+      }
+      pack_store(Pack{a.pack_off, a.pack_dst, a.pack_mode}, f.e, pa);
+    }
+  } else {
+    const float4* p4 = reinterpret_cast<const float4*>(a.p);
+    const float4* g4 = reinterpret_cast<const float4*>(a.g);
+    const float4* m4 = reinterpret_cast<const float4*>(a.m);
+    const float4* v4 = reinterpret_cast<const float4*>(a.v);
+    const long long mb = (int)blockIdx.x - a.nfb;
+    long long ic = mb * 256 + threadIdx.x;
+    const long long istride = (long long)a.nmain * 256;
+    if (mb * 256 < a.n4c) {                            // block-uniform; false only for an empty buffer
+      // iteration 0 leads: unconditional loads (a ragged last block reads its last float4 again)
+      const bool on = ic < a.n4c;
+      const long long i = hole_map(a.holes, on ? ic : a.n4c - 1);
+      const float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
+      __builtin_amdgcn_sched_barrier(0);
+      t = a.bump < 0 ? s0 : s0 + 1;
+      const AdamStep c = adam_step(a, t);
+      if (on) adam_f4<NTP>(a, c, i, pp, gg, mm, vv);
+      for (ic += istride; ic < a.n4c; ic += istride) {
+        const long long i2 = hole_map(a.holes, ic);
+        adam_f4<NTP>(a, c, i2, p4[i2], g4[i2], m4[i2], v4[i2]);
+      }
+    } else {
+      t = a.bump < 0 ? s0 : s0 + 1;
+    }
+  }
+  if (a.bump > 0 && last_block(a.arrive, t) && threadIdx.x == 0) {
+    a.step[0] = t;
+    for (int c = 1; c < a.bump; ++c) a.step[c] += 1;   // extra device counters (e.g. batch position)
+    *a.arrive = 0u;
+  }
+  if constexpr (PROF) {
+    if (threadIdx.x == 0) a.prof[(size_t)blockIdx.x * 8 + 1] = __builtin_amdgcn_s_memrealtime();
+  }
+}
+
 __device__ __forceinline__ void sgd_elem(float& p, float& b, float d, float lr, float momentum, float dampening,
                                          float wd, int nesterov, long long t) {
   if (wd != 0.f) d = d + wd * p;
   if (momentum != 0.f) {
-    b = (t == 1) ? d : momentum * b + (1.f - dampening) * d;
+    // a sum of two products: pinned to the contraction hipcc has always chosen here (momentum * b rounded first)
+    b = (t == 1) ? d : __builtin_fmaf(1.f - dampening, d, momentum * b);
     d = nesterov ? d + momentum * b : b;
   }
   p = p - lr * d;
@@ -301,50 +499,82 @@ __device__ __forceinline__ void sgd_elem(float& p, float& b, float d, float lr, 
 
 // torch.optim.SGD semantics (torch/optim/sgd.py): d_p = g + wd*p; buf = momentum*buf + (1-dampening)*d_p
 // (buf = d_p on the first step); d_p = nesterov ? d_p + momentum*buf : buf; p -= lr*d_p.
-__global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
-                                             long long n4, float lr, float momentum, float dampening, float wd,
-                                             int nesterov, float grad_scale, long long* __restrict__ step,
-                                             unsigned* __restrict__ arrive, int bump, Pack pk, Fold fd,
-                                             const float* __restrict__ lr_tab, int lr_len) {
-  const long long t = bump < 0 ? *step : *step + 1;
-  lr = sched_lr(lr, lr_tab, lr_len, t);
-  float4* p4 = reinterpret_cast<float4*>(p);
-  float4* g4 = reinterpret_cast<float4*>(g);
-  float4* b4 = reinterpret_cast<float4*>(buf);
-  const Holes holes = make_holes(fd);
-  const long long n4c = n4 - holes.len[0] - holes.len[1];
-  const int nfb = fold_blocks(fd.f[0]) + fold_blocks(fd.f[1]);
-  const int fb = (int)blockIdx.x - ((int)gridDim.x - nfb);
-  if (fb >= 0) {                                       // fold block (see fold_lane)
-    const FoldLane fl = fold_lane(fd, g, fb);
-    if (fl.e >= 0) {
-      float pa = p[fl.e], ba = momentum != 0.f ? buf[fl.e] : 0.f;
-      sgd_elem(pa, ba, fl.g * grad_scale, lr, momentum, dampening, wd, nesterov, t);
-      p[fl.e] = pa;
-      if (momentum != 0.f) buf[fl.e] = ba;
-      g[fl.e] = fl.g;
-      pack_store(pk, fl.e, pa);
+// Same argument struct and block order as the lean Adam kernel (fold blocks first, iteration 0's
+// loads ahead of the wait for the step counter).  MOM: momentum != 0, the buffer exists.
+template <bool MOM>
+__device__ __forceinline__ void sgd_f4(const Lean& a, float lr, long long t, long long i, float4 pp, float4 gg,
+                                       float4 bb) {
+  const Pack pk{a.pack_off, a.pack_dst, a.pack_mode};
+  float* pa = &pp.x; float* ga = &gg.x; float* ba = &bb.x;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    sgd_elem(pa[j], ba[j], ga[j] * a.grad_scale, lr, MOM ? a.a : 0.f, a.b, a.wd, a.flag, t);
+    pack_store(pk, 4 * i + j, pa[j]);
+  }
+  reinterpret_cast<float4*>(a.p)[i] = pp;
+  if constexpr (MOM) reinterpret_cast<float4*>(a.m)[i] = bb;
+}
+
+// a main block of k_sgd; returns the step t
+template <bool MOM>
+__device__ __forceinline__ long long sgd_main(const Lean& a, long long s0) {
+  const float4* p4 = reinterpret_cast<const float4*>(a.p);
+  const float4* g4 = reinterpret_cast<const float4*>(a.g);
+  const float4* b4 = reinterpret_cast<const float4*>(a.m);
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  const long long mb = (int)blockIdx.x - a.nfb;
+  long long ic = mb * 256 + threadIdx.x;
+  const long long istride = (long long)a.nmain * 256;
+  if (mb * 256 >= a.n4c) return a.bump < 0 ? s0 : s0 + 1;   // block-uniform; only for an empty buffer
+  const bool on = ic < a.n4c;                          // a ragged last block reads its last float4 again
+  const long long i = hole_map(a.holes, on ? ic : a.n4c - 1);
+  const float4 pp = p4[i], gg = g4[i];
+  const float4 bb = MOM ? b4[i] : zero;
+  __builtin_amdgcn_sched_barrier(0);
+  const long long t = a.bump < 0 ? s0 : s0 + 1;
+  const float lr = sched_lr(a.lr, a.lr_tab, a.lr_len, t);
+  if (on) sgd_f4<MOM>(a, lr, t, i, pp, gg, bb);
+  for (ic += istride; ic < a.n4c; ic += istride) {
+    const long long i2 = hole_map(a.holes, ic);
+    sgd_f4<MOM>(a, lr, t, i2, p4[i2], g4[i2], MOM ? b4[i2] : zero);
+  }
+  return t;
+}
+
+__global__ __launch_bounds__(256) void k_sgd(const Lean a) {
+  const long long s0 = *a.step;
+  long long f_off[2] = {a.f_off[0], a.f_off[1]};
+  asm("" : "+s"(f_off[0]), "+s"(f_off[1]));            // fetched with the other arguments, not on the fold path
+  __builtin_amdgcn_sched_barrier(0);
+  const float momentum = a.a;
+  long long t;
+  if ((int)blockIdx.x < a.nfb) {                       // fold block
+    const LeanFold f = lean_fold_addr(a, f_off, blockIdx.x);
+    float pa = 0.f, ba = 0.f;
+    if (f.e >= 0) {
+      pa = a.p[f.e];
+      if (momentum != 0.f) ba = a.m[f.e];
+    }
+    float4 x[kMaxFold / kLS];
+    lean_fold_load(f, x);
+    __builtin_amdgcn_sched_barrier(0);
+    t = a.bump < 0 ? s0 : s0 + 1;
+    const float lr = sched_lr(a.lr, a.lr_tab, a.lr_len, t);
+    const float gf = lean_fold_sum(f, x);
+    if (f.e >= 0) {
+      sgd_elem(pa, ba, gf * a.grad_scale, lr, momentum, a.b, a.wd, a.flag, t);
+      a.p[f.e] = pa;
+      if (momentum != 0.f) a.m[f.e] = ba;
+      a.g[f.e] = gf;
+      pack_store(Pack{a.pack_off, a.pack_dst, a.pack_mode}, f.e, pa);
     }
   } else {
-    const long long istride = (long long)(gridDim.x - nfb) * blockDim.x;
-    for (long long ic = (long long)blockIdx.x * blockDim.x + threadIdx.x; ic < n4c; ic += istride) {
-      const long long i = hole_map(holes, ic);
-      float4 pp = p4[i], gg = g4[i];
-      float4 bb = momentum != 0.f ? b4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-      float* pa = &pp.x; float* ga = &gg.x; float* ba = &bb.x;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        sgd_elem(pa[j], ba[j], ga[j] * grad_scale, lr, momentum, dampening, wd, nesterov, t);
-        pack_store(pk, 4 * i + j, pa[j]);
-      }
-      p4[i] = pp;
-      if (momentum != 0.f) b4[i] = bb;
-    }
+    t = momentum != 0.f ? sgd_main<true>(a, s0) : sgd_main<false>(a, s0);
   }
-  if (bump > 0 && last_block(arrive, t) && threadIdx.x == 0) {
-    step[0] = t;
-    for (int c = 1; c < bump; ++c) step[c] += 1;   // extra device counters (e.g. batch position)
-    *arrive = 0u;
+  if (a.bump > 0 && last_block(a.arrive, t) && threadIdx.x == 0) {
+    a.step[0] = t;
+    for (int c = 1; c < a.bump; ++c) a.step[c] += 1;   // extra device counters (e.g. batch position)
+    *a.arrive = 0u;
   }
 }
 
@@ -368,9 +598,32 @@ inline int grid_for(long long n4) {
   return (int)blocks;
 }
 
+// geometry of a lean launch; the hyper-parameters are filled in by the caller
+Lean lean_args(float* p, float* g, float* m, float* v, long long n4, long long* step, unsigned* arrive, int bump,
+               const Pack& pk, const Fold& fd, const float* lr_tab, int lr_len) {
+  Lean a{};
+  a.p = p; a.g = g; a.m = m; a.v = v;
+  a.step = step; a.arrive = arrive; a.bump = bump;
+  a.lr_tab = lr_tab; a.lr_len = lr_len;
+  a.pack_dst = pk.dst; a.pack_off = pk.off; a.pack_mode = pk.mode;
+  a.holes = make_holes(fd);
+  a.n4c = n4 - a.holes.len[0] - a.holes.len[1];
+  for (int k = 0; k < 2; ++k) {
+    a.f_off[k] = fd.f[k].off; a.f_len[k] = fd.f[k].len; a.f_nrep[k] = fd.f[k].nrep; a.f_s4[k] = fd.f[k].stride / 4;
+  }
+  a.nfb0 = fold_blocks(fd.f[0]);
+  a.nfb = a.nfb0 + fold_blocks(fd.f[1]);
+  a.nmain = grid_for(a.n4c);
+  return a;
+}
+
+bool g_force_general = false;   // pde_optim_force_general
+
 }  // namespace
 
 extern "C" {
+
+void pde_optim_force_general(int on) { g_force_general = on != 0; }
 
 hipError_t pde_adam_flat(float* p, float* g, float* m, float* v, long long n, float lr, float b1, float b2,
                          float eps, float wd, int decoupled, float grad_scale, long long* step, unsigned* arrive,
@@ -406,16 +659,28 @@ hipError_t pde_adam_flat(float* p, float* g, float* m, float* v, long long n, fl
     return e != nullptr && e[0] == '1';   // default off: neutral in a same-box A/B (profiles/r5_lenet/)
   }();
 #define PDE_ADAM_LAUNCH(P, N)                                                                                   \
-  hipLaunchKernelGGL((k_adam<P, N>), dim3(grid_for(n4c) + ar.nvb + nfb), dim3(256), 0, st, p, g, m, v, n4, lr, b1, \
+  hipLaunchKernelGGL((k_adam<P, N, true>), dim3(grid_for(n4c) + ar.nvb + nfb), dim3(256), 0, st, p, g, m, v, n4, lr, b1, \
                      b2, eps, wd, decoupled, grad_scale, step, arrive, bump, Pack{pack_off, pack_dst, pack_mode},    \
                      Fold{{Fold1{fold_off, fold_len, fold_nrep, fold_stride},                                      \
                            Fold1{fold2_off, fold2_len, fold2_nrep, fold2_stride}}},                                \
                      ar, P ? prof : nullptr, lr_tab, lr_len)
-  if (prof) {
+#define PDE_ADAM_LEAN(P, N) hipLaunchKernelGGL((k_adam<P, N, false>), dim3(la.nfb + la.nmain), dim3(256), 0, st, la)
+  if (ar.nvb == 0 && !g_force_general) {   // no peer: the lean kernel
+    Lean la = lean_args(p, g, m, v, n4, step, arrive, bump, Pack{pack_off, pack_dst, pack_mode}, fdh, lr_tab, lr_len);
+    la.prof = prof;
+    la.lr = lr; la.grad_scale = grad_scale; la.wd = wd; la.flag = decoupled;
+    la.a = b1; la.b = b2; la.oma = 1.f - b1; la.omb = 1.f - b2; la.eps = eps;
+    if (prof) {
+      if (ntp) PDE_ADAM_LEAN(true, true); else PDE_ADAM_LEAN(true, false);
+    } else {
+      if (ntp) PDE_ADAM_LEAN(false, true); else PDE_ADAM_LEAN(false, false);
+    }
+  } else if (prof) {
     if (ntp) PDE_ADAM_LAUNCH(true, true); else PDE_ADAM_LAUNCH(true, false);
   } else {
     if (ntp) PDE_ADAM_LAUNCH(false, true); else PDE_ADAM_LAUNCH(false, false);
   }
+#undef PDE_ADAM_LEAN
 #undef PDE_ADAM_LAUNCH
   return hipGetLastError();
 }
@@ -429,16 +694,14 @@ hipError_t pde_sgd_flat(float* p, float* g, float* buf, long long n, float lr, f
   if (lr_tab != nullptr && lr_len < 1) return hipErrorInvalidValue;
   const long long n4 = n / 4;
   const Fold fdh{{Fold1{fold_off, fold_len, fold_nrep, fold_stride}, Fold1{fold2_off, fold2_len, fold2_nrep, fold2_stride}}};
-  const Holes hh = make_holes(fdh);
   for (int k = 0; k < 2; ++k)
     if (fold_on(fdh.f[k]) && (fdh.f[k].off % 4 || fdh.f[k].stride % 4 || fdh.f[k].nrep > kMaxFold ||
                               fdh.f[k].off + (long long)fdh.f[k].nrep * fdh.f[k].stride > n))
       return hipErrorInvalidValue;
-  const int nfb = fold_blocks(fdh.f[0]) + fold_blocks(fdh.f[1]);
-  hipLaunchKernelGGL(k_sgd, dim3(grid_for(n4 - hh.len[0] - hh.len[1]) + nfb), dim3(256), 0, st, p, g, buf, n4, lr, momentum, dampening, wd,
-                     nesterov, grad_scale, step, arrive, bump, Pack{pack_off, pack_dst, pack_mode},
-                     Fold{{Fold1{fold_off, fold_len, fold_nrep, fold_stride}, Fold1{fold2_off, fold2_len, fold2_nrep, fold2_stride}}},
-                     lr_tab, lr_len);
+  Lean la = lean_args(p, g, buf, nullptr, n4, step, arrive, bump, Pack{pack_off, pack_dst, pack_mode}, fdh, lr_tab, lr_len);
+  la.lr = lr; la.grad_scale = grad_scale; la.wd = wd; la.flag = nesterov;
+  la.a = momentum; la.b = dampening;
+  hipLaunchKernelGGL(k_sgd, dim3(la.nfb + la.nmain), dim3(256), 0, st, la);
   return hipGetLastError();
 }
 

@@ -633,6 +633,8 @@ PYBIND11_MODULE(_kernels, m) {
         py::arg("peer_dev") = py::none(), py::arg("ar_off") = 0, py::arg("ar_epoch") = py::none(),
         py::arg("ar_two") = 0, py::arg("pack_mode") = 1, py::arg("fold2_off") = -1, py::arg("fold2_len") = 0,
         py::arg("fold2_nrep") = 1, py::arg("fold2_stride") = 0, py::arg("lr_table") = py::none());
+  m.def("optim_force_general", [](bool on) { pde_optim_force_general(on ? 1 : 0); }, py::arg("on"),
+        "adam_flat calls without peer_dev take the general (fused all-reduce) kernel instead of the lean one");
   m.def("sgd_flat", &sgd_flat, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("lr"), py::arg("momentum"),
         py::arg("dampening"), py::arg("wd"), py::arg("nesterov"), py::arg("grad_scale"), py::arg("step"),
         py::arg("arrive"), py::arg("bump"), py::arg("pack_off") = -1, py::arg("pack_dst") = py::none(),

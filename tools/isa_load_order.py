@@ -12,7 +12,9 @@ and, for every kernel whose name contains one of the given substrings, prints
   are left out unless ``--all-blocks`` is given).  With ``--lds`` the LDS side is listed too:
   ``ds_read*`` (``r``), ``ds_write*`` (``d``), lane exchanges -- ``ds_bpermute`` / ``ds_permute`` /
   ``ds_swizzle`` and DPP moves -- (``x``) and ``s_waitcnt lgkmcnt(n)`` (``g<n>``; a wait on both
-  counters prints ``w<n> g<m>``).
+  counters prints ``w<n> g<m>``).  With ``--scalar`` the scalar loads (``s_load_*``) are listed as ``s``
+  next to the same ``g<n>`` waits, so a prologue that fetches its kernel arguments in several
+  dependent rounds shows ``7s g0 1s g0 br 4s g0 ...`` ahead of its first ``L``.
 
 A kernel that issues all its loads before the first MFMA shows ``26L`` ahead of the first ``M``;
 one that the compiler serialised shows ``4L w0 8M 4L w0 ...``.
@@ -20,6 +22,7 @@ one that the compiler serialised shows ``4L w0 8M 4L w0 ...``.
     python tools/isa_load_order.py csrc/kernels/lenet.hip k_fc1_fwd k_fc_bwd
     python tools/isa_load_order.py csrc/kernels/optim.hip k_adam k_sgd --out profiles/x.txt
     python tools/isa_load_order.py csrc/kernels/lenet_v2.hip k_conv_fwd2 --lds
+    python tools/isa_load_order.py csrc/kernels/optim.hip k_adam k_sgd --scalar --lds --all-blocks
 """
 import argparse
 import os
@@ -36,6 +39,7 @@ _TOKEN = re.compile(
 _TOKEN_LDS = re.compile(
     r"^\s*(global_load\w*|buffer_load\w*|\w*_store\w*|\w*_atomic\w*|s_waitcnt|v_mfma\w*|s_barrier|s_cbranch\w*"
     r"|ds_\w+|v_\w+_dpp)\b(.*)$")
+_TOKEN_SCALAR = re.compile(r"^\s*(s_load_\w+)\b(.*)$")
 _LABEL = re.compile(r"^([.\w$]+):")
 _REMARK = re.compile(r"remark:\s+(.+?): (\S+)(?: \[-Rpass[^\]]*\])?\s*$")
 _KEYS = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]",
@@ -88,8 +92,11 @@ def resources(remarks):
     return res
 
 
-def classify_lds(op, rest):
-    """Tokens of one instruction with --lds: the plain token (if any) and the LDS-side ones."""
+def classify_lds(op, rest, lds=True):
+    """Tokens of one instruction with --lds / --scalar: the plain token (if any), lgkmcnt waits and,
+    with ``lds``, the LDS-side ones."""
+    if op.startswith("s_load_"):
+        return ["s"]
     if op == "s_waitcnt":
         toks = []
         m = re.search(r"vmcnt\((\d+)\)", rest)
@@ -100,8 +107,10 @@ def classify_lds(op, rest):
             toks.append(f"g{m.group(1)}")
         return toks
     if op.endswith("_dpp"):
-        return ["x"]
+        return ["x"] if lds else []
     if op.startswith("ds_"):
+        if not lds:
+            return []
         if re.match(r"ds_(bpermute|permute|swizzle)", op):
             return ["x"]
         if re.match(r"ds_(read|load)", op):
@@ -154,12 +163,12 @@ def rle(tokens):
         while j < len(tokens) and tokens[j] == tokens[i]:
             j += 1
         n = j - i
-        out.append(f"{n}{tokens[i]}" if n > 1 or tokens[i] in ("L", "S", "M", "A", "r", "d", "x") else tokens[i])
+        out.append(f"{n}{tokens[i]}" if n > 1 or tokens[i] in ("L", "S", "M", "A", "r", "d", "x", "s") else tokens[i])
         i = j
     return " ".join(out)
 
 
-def order(lines, all_blocks=False, lds=False):
+def order(lines, all_blocks=False, lds=False, scalar=False):
     """[(block label, rle string)] for the basic blocks that hold any matched instruction."""
     blocks, label, toks = [], "entry", []
 
@@ -173,10 +182,10 @@ def order(lines, all_blocks=False, lds=False):
                 blocks.append((label, rle(toks)))
             label, toks = m.group(1), []
             continue
-        m = (_TOKEN_LDS if lds else _TOKEN).match(line)
+        m = (_TOKEN_SCALAR.match(line) if scalar else None) or (_TOKEN_LDS if lds or scalar else _TOKEN).match(line)
         if m:
-            if lds:
-                toks.extend(classify_lds(m.group(1), m.group(2)))
+            if lds or scalar:
+                toks.extend(classify_lds(m.group(1), m.group(2), lds))
             else:
                 t = classify(m.group(1), m.group(2))
                 if t:
@@ -186,7 +195,7 @@ def order(lines, all_blocks=False, lds=False):
     return blocks
 
 
-def report(src, wanted, extra=(), all_blocks=False, lds=False):
+def report(src, wanted, extra=(), all_blocks=False, lds=False, scalar=False):
     asm, remarks = compile_to_asm(src, file_flags(src) + list(extra))
     res = resources(remarks)
     bodies = kernel_bodies(asm)
@@ -198,7 +207,7 @@ def report(src, wanted, extra=(), all_blocks=False, lds=False):
             continue
         out.append(f"== {pretty[n]}")
         out.append("   " + "  ".join(f"{k.split(' [')[0]}={res[n].get(k, '?')}" for k in _KEYS))
-        for label, seq in order(bodies[n], all_blocks, lds):
+        for label, seq in order(bodies[n], all_blocks, lds, scalar):
             out.append(f"   {label:>10}: {seq}")
         out.append("")
     if not out:
@@ -215,9 +224,11 @@ def main(argv=None):
     ap.add_argument("--all-blocks", action="store_true", help="also list blocks that hold only branches")
     ap.add_argument("--lds", action="store_true",
                     help="also list LDS reads (r), writes (d), lane exchanges (x) and lgkmcnt waits (g<n>)")
+    ap.add_argument("--scalar", action="store_true",
+                    help="also list scalar loads (s) and lgkmcnt waits (g<n>)")
     ap.add_argument("-q", "--quiet", action="store_true", help="with --out: do not print the report")
     a = ap.parse_args(argv)
-    text = report(a.source, a.kernels, a.extra, a.all_blocks, a.lds)
+    text = report(a.source, a.kernels, a.extra, a.all_blocks, a.lds, a.scalar)
     if not (a.quiet and a.out):
         print(text)
     if a.out:
