@@ -38,21 +38,23 @@ void pde_lenet_set_prof(unsigned long long* buf);
 unsigned long long* pde_lenet_prof_slot(int kid);
 
 // ---- optimizers: csrc/kernels/optim.hip ----
-// fold_*: gradient replicas folded before the update: for e in [fold_off, fold_off + fold_len),
-// g[e] = sum_{r < fold_nrep} g[e + r * fold_stride] (written back); replica storage r >= 1 is skipped.
-// lr_tab / lr_len (all four optimizers; nullable): device table of per-step learning rates, optimizer step t
-// (1-based) uses lr_tab[min(t-1, lr_len-1)] in place of the by-value lr (pde_lr.h).
-hipError_t pde_adam_flat(float* p, float* g, float* m, float* v, long long n, float lr, float b1, float b2,
-                         float eps, float wd, int decoupled, float grad_scale, long long* step, unsigned* arrive,
-                         int bump, long long pack_off, float* pack_dst, long long fold_off, int fold_len,
-                         int fold_nrep, int fold_stride, const void* peer_dev, long long ar_off,
-                         long long* ar_epoch, int ar_two, int pack_mode, long long fold2_off, int fold2_len,
-                         int fold2_nrep, int fold2_stride, const float* lr_tab, int lr_len, hipStream_t st);
-hipError_t pde_sgd_flat(float* p, float* g, float* buf, long long n, float lr, float momentum, float dampening,
-                        float wd, int nesterov, float grad_scale, long long* step, unsigned* arrive, int bump,
-                        long long pack_off, float* pack_dst, long long fold_off, int fold_len, int fold_nrep,
-                        int fold_stride, int pack_mode, long long fold2_off, int fold2_len, int fold2_nrep,
-                        int fold2_stride, const float* lr_tab, int lr_len, hipStream_t st);
+// Gradient replicas folded before the update: for e in [off, off + len), g[e] = sum_{r < nrep} g[e + r * stride]
+// (written back); replica storage r >= 1 is skipped.  off < 0 or nrep <= 1: none.
+typedef struct PdeFold { long long off; int len, nrep, stride; } PdeFold;
+// What both flat optimizers take.  lr_tab / lr_len (all four optimizers; nullable): device table of per-step
+// learning rates, optimizer step t (1-based) uses lr_tab[min(t-1, lr_len-1)] in place of the by-value lr (pde_lr.h).
+typedef struct PdeFlatOpt {
+  float *p, *g, *m, *v;            // SGD: m = momentum buffer, v unused
+  long long n;
+  float lr, wd, grad_scale;
+  long long* step; unsigned* arrive; int bump;
+  long long pack_off; float* pack_dst; int pack_mode;   // pack_off < 0: no conv2 weight repack
+  PdeFold fold[2];
+  const float* lr_tab; int lr_len;
+} PdeFlatOpt;
+hipError_t pde_adam_flat(const PdeFlatOpt* o, float b1, float b2, float eps, int decoupled, const void* peer_dev,
+                         long long ar_off, long long* ar_epoch, int ar_two, hipStream_t st);
+hipError_t pde_sgd_flat(const PdeFlatOpt* o, float momentum, float dampening, int nesterov, hipStream_t st);
 hipError_t pde_lenet_pack_w2(const float* w2, float* dst, hipStream_t st);
 // pde_adam_flat without peer_dev runs the lean kernel (no all-reduce code compiled in); on != 0 makes such
 // calls take the general kernel (the one of the fused all-reduce routes, with no side blocks) instead.

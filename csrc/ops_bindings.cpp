@@ -199,6 +199,45 @@ void lenet_conv_bwd(const at::Tensor& X, const at::Tensor& rows, const at::Tenso
 }
 
 // ------------------------------------------------------------------------------------------------
+// The tensor-level checks adam_flat and sgd_flat share, and their PdeFlatOpt.  m (m_name, at least m_n
+// elements) is exp_avg or the momentum buffer; v is Adam's exp_avg_sq, null for SGD.
+// fold[k] = {off, len, nrep, stride} as the caller gave them.
+PdeFlatOpt flat_opt(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const char* m_name, int64_t m_n,
+                    const at::Tensor* v, double lr, double wd, double grad_scale, const at::Tensor& step,
+                    const at::Tensor& arrive, int64_t bump, int64_t pack_off, const OptT& pack_dst, int64_t pack_mode,
+                    const int64_t (&fold)[2][4], const OptT& lr_tab) {
+  const int64_t n = p.numel();
+  PdeFlatOpt o{};
+  check_cuda(p, "params", F32);
+  o.lr_tab = pde::lr_table(lr_tab, p, &o.lr_len);
+  check_cuda(g, "grads", F32, n);
+  check_cuda(m, m_name, F32, m_n);
+  for (int k = 0; k < 2; ++k) {
+    const int64_t off = fold[k][0], len = fold[k][1], nrep = fold[k][2], stride = fold[k][3];
+    if (off >= 0 && nrep > 1)
+      TORCH_CHECK(off % 4 == 0 && len % 4 == 0 && stride % 4 == 0 && len <= stride && off + stride * nrep <= n &&
+                      nrep <= 16,
+                  k ? "bad second gradient fold layout (at most 16 replicas)"
+                    : "bad gradient fold layout (at most 16 replicas)");
+    o.fold[k] = PdeFold{off, (int)len, (int)nrep, (int)stride};
+  }
+  if (v) check_cuda(*v, "exp_avg_sq", F32, n);
+  check_cuda(step, "step", I64, std::max<int64_t>(1, bump));
+  TORCH_CHECK(bump >= -1, "bump must be >= -1");
+  check_cuda(arrive, "arrive", I32, 1);
+  TORCH_CHECK(n % 4 == 0, "flat buffer length must be a multiple of 4");
+  TORCH_CHECK(pack_mode == 1 || pack_mode == 2, "pack_mode must be 1 ([500][64]) or 2 (lenet_v2 image)");
+  o.pack_dst = optr<float>(pack_dst, "pack_dst", F32, pack_mode == 2 ? kPdeWpFloats : 500 * 64);
+  if (pack_off >= 0) TORCH_CHECK(o.pack_dst && pack_off + 25000 <= n, "bad pack target");
+  o.pack_off = o.pack_dst ? pack_off : -1;
+  o.pack_mode = (int)pack_mode;
+  o.p = ptr<float>(p); o.g = ptr<float>(g); o.m = ptr<float>(m); o.v = v ? ptr<float>(*v) : nullptr;
+  o.n = n;
+  o.lr = (float)lr; o.wd = (float)wd; o.grad_scale = (float)grad_scale;
+  o.step = ptr<long long>(step); o.arrive = ptr<unsigned>(arrive); o.bump = (int)bump;
+  return o;
+}
+
 void adam_flat(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v, double lr,
                double b1, double b2, double eps, double wd, bool decoupled, double grad_scale, const at::Tensor& step,
                const at::Tensor& arrive, int64_t bump, int64_t pack_off, const OptT& pack_dst, int64_t fold_off,
@@ -222,32 +261,11 @@ void adam_flat(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, co
     pdev = peer_dev->data_ptr();
     ep = ptr<long long>(*ar_epoch);
   }
-  check_cuda(p, "params", F32);
-  int lr_len = 0;
-  const float* lrt = pde::lr_table(lr_tab, p, &lr_len);
-  check_cuda(g, "grads", F32, n);
-  check_cuda(m, "exp_avg", F32, n);
-  if (fold_off >= 0 && fold_nrep > 1)
-    TORCH_CHECK(fold_off % 4 == 0 && fold_len % 4 == 0 && fold_stride % 4 == 0 && fold_len <= fold_stride &&
-                    fold_off + fold_stride * fold_nrep <= n && fold_nrep <= 16,
-                "bad gradient fold layout (at most 16 replicas)");
-  if (fold2_off >= 0 && fold2_nrep > 1)
-    TORCH_CHECK(fold2_off % 4 == 0 && fold2_len % 4 == 0 && fold2_stride % 4 == 0 && fold2_len <= fold2_stride &&
-                    fold2_off + fold2_stride * fold2_nrep <= n && fold2_nrep <= 16,
-                "bad second gradient fold layout (at most 16 replicas)");
-  check_cuda(v, "exp_avg_sq", F32, n);
-  check_cuda(step, "step", I64, std::max<int64_t>(1, bump));
-  TORCH_CHECK(bump >= -1, "bump must be >= -1");
-  check_cuda(arrive, "arrive", I32, 1);
-  TORCH_CHECK(n % 4 == 0, "flat buffer length must be a multiple of 4");
-  TORCH_CHECK(pack_mode == 1 || pack_mode == 2, "pack_mode must be 1 ([500][64]) or 2 (lenet_v2 image)");
-  float* pd = optr<float>(pack_dst, "pack_dst", F32, pack_mode == 2 ? kPdeWpFloats : 500 * 64);
-  if (pack_off >= 0) TORCH_CHECK(pd && pack_off + 25000 <= n, "bad pack target");
-  hip_check(pde_adam_flat(ptr<float>(p), ptr<float>(g), ptr<float>(m), ptr<float>(v), n, (float)lr, (float)b1,
-                          (float)b2, (float)eps, (float)wd, decoupled ? 1 : 0, (float)grad_scale, ptr<long long>(step),
-                          ptr<unsigned>(arrive), (int)bump, pd ? pack_off : -1, pd, fold_off, (int)fold_len,
-                          (int)fold_nrep, (int)fold_stride, pdev, ar_off, ep, (int)ar_two, (int)pack_mode, fold2_off,
-                          (int)fold2_len, (int)fold2_nrep, (int)fold2_stride, lrt, lr_len, cur_stream()),
+  const PdeFlatOpt o = flat_opt(p, g, m, "exp_avg", n, &v, lr, wd, grad_scale, step, arrive, bump, pack_off, pack_dst,
+                                pack_mode, {{fold_off, fold_len, fold_nrep, fold_stride},
+                                            {fold2_off, fold2_len, fold2_nrep, fold2_stride}}, lr_tab);
+  hip_check(pde_adam_flat(&o, (float)b1, (float)b2, (float)eps, decoupled ? 1 : 0, pdev, ar_off, ep, (int)ar_two,
+                          cur_stream()),
             "adam_flat");
 }
 
@@ -256,33 +274,11 @@ void sgd_flat(const at::Tensor& p, const at::Tensor& g, const at::Tensor& buf, d
               const at::Tensor& arrive, int64_t bump, int64_t pack_off, const OptT& pack_dst, int64_t fold_off,
               int64_t fold_len, int64_t fold_nrep, int64_t fold_stride, int64_t pack_mode, int64_t fold2_off,
               int64_t fold2_len, int64_t fold2_nrep, int64_t fold2_stride, const OptT& lr_tab) {
-  const int64_t n = p.numel();
-  check_cuda(p, "params", F32);
-  int lr_len = 0;
-  const float* lrt = pde::lr_table(lr_tab, p, &lr_len);
-  check_cuda(g, "grads", F32, n);
-  check_cuda(buf, "momentum_buffer", F32, momentum != 0.0 ? n : 0);
-  if (fold_off >= 0 && fold_nrep > 1)
-    TORCH_CHECK(fold_off % 4 == 0 && fold_len % 4 == 0 && fold_stride % 4 == 0 && fold_len <= fold_stride &&
-                    fold_off + fold_stride * fold_nrep <= n && fold_nrep <= 16,
-                "bad gradient fold layout (at most 16 replicas)");
-  if (fold2_off >= 0 && fold2_nrep > 1)
-    TORCH_CHECK(fold2_off % 4 == 0 && fold2_len % 4 == 0 && fold2_stride % 4 == 0 && fold2_len <= fold2_stride &&
-                    fold2_off + fold2_stride * fold2_nrep <= n && fold2_nrep <= 16,
-                "bad second gradient fold layout (at most 16 replicas)");
-  check_cuda(step, "step", I64, std::max<int64_t>(1, bump));
-  TORCH_CHECK(bump >= -1, "bump must be >= -1");
-  check_cuda(arrive, "arrive", I32, 1);
-  TORCH_CHECK(n % 4 == 0, "flat buffer length must be a multiple of 4");
-  TORCH_CHECK(pack_mode == 1 || pack_mode == 2, "pack_mode must be 1 ([500][64]) or 2 (lenet_v2 image)");
-  float* pd = optr<float>(pack_dst, "pack_dst", F32, pack_mode == 2 ? kPdeWpFloats : 500 * 64);
-  if (pack_off >= 0) TORCH_CHECK(pd && pack_off + 25000 <= n, "bad pack target");
-  hip_check(pde_sgd_flat(ptr<float>(p), ptr<float>(g), ptr<float>(buf), n, (float)lr, (float)momentum,
-                         (float)dampening, (float)wd, nesterov ? 1 : 0, (float)grad_scale, ptr<long long>(step),
-                         ptr<unsigned>(arrive), (int)bump, pd ? pack_off : -1, pd, fold_off, (int)fold_len,
-                         (int)fold_nrep, (int)fold_stride, (int)pack_mode, fold2_off, (int)fold2_len,
-                         (int)fold2_nrep, (int)fold2_stride, lrt, lr_len, cur_stream()),
-            "sgd_flat");
+  const PdeFlatOpt o = flat_opt(p, g, buf, "momentum_buffer", momentum != 0.0 ? p.numel() : 0, nullptr, lr, wd,
+                                grad_scale, step, arrive, bump, pack_off, pack_dst, pack_mode,
+                                {{fold_off, fold_len, fold_nrep, fold_stride},
+                                 {fold2_off, fold2_len, fold2_nrep, fold2_stride}}, lr_tab);
+  hip_check(pde_sgd_flat(&o, (float)momentum, (float)dampening, nesterov ? 1 : 0, cur_stream()), "sgd_flat");
 }
 
 void lenet_pack_w2_v2(const at::Tensor& w2, const at::Tensor& dst) {
