@@ -2,6 +2,7 @@
 // Every entry validates device / dtype / contiguity / shape before launching on the current stream.
 #include "pde_bind.h"
 #include "pde_kernels.h"
+#include "pde_loss.h"
 
 namespace pde {
 namespace {
@@ -117,17 +118,67 @@ void gelu_bwd(const at::Tensor& dY, const at::Tensor& X, const at::Tensor& dX) {
   hip_check(pde_gelu_bwd(dY.data_ptr(), X.data_ptr(), dX.data_ptr(), X.numel(), cur_stream()), "gelu_bwd");
 }
 
+// scale_dev (fp32 [1], e.g. the inv word of loss_targets' info block): the masked-loss kernels
 void xent_bf16(const at::Tensor& logits, const at::Tensor& tgt, int64_t V, double scale, const at::Tensor& loss_rows,
-               bool write_grad) {
+               bool write_grad, const OptT& scale_dev) {
   check_cuda(logits, "logits", BF16);
   TORCH_CHECK(logits.dim() == 2 && logits.size(1) % 8 == 0, "logits must be [N, Vp] with Vp % 8 == 0");
   const int64_t N = logits.size(0), Vp = logits.size(1);
   TORCH_CHECK(V <= Vp, "V > padded vocab");
   check_cuda(tgt, "targets", I64, N);
   check_cuda(loss_rows, "loss_rows", F32, N);
+  TORCH_CHECK(V >= 0 && N <= INT32_MAX && Vp <= INT32_MAX, "xent_bf16: N, Vp and V must fit 32 bits");
+  const float* sd = optr<float>(scale_dev, "scale_dev", F32, 1);
+  TORCH_CHECK(tgt.device() == logits.device() && loss_rows.device() == logits.device() &&
+                  (sd == nullptr || scale_dev->device() == logits.device()),
+              "xent_bf16: all tensors must be on the logits' device");
   hip_check(pde_xent_bf16(logits.data_ptr(), ptr<int64_t>(tgt), (int)N, (int)Vp, (int)V, (float)scale,
-                          ptr<float>(loss_rows), write_grad, cur_stream()),
+                          ptr<float>(loss_rows), write_grad, sd, cur_stream()),
             "xent_bf16");
+}
+
+// Masked loss (pde_loss.h): eff (int64 [N]) <- the target where it counts, else -1; info (int32 [4]) <- the
+// info block {count, inv as fp32 bits, out_of_range, 0}.  ignore_index = None: no ignored value.  loss_mask:
+// uint8 or bool [N].  doc_end: int32 [N] of rows of T (given only when document ends are masked).
+void loss_targets(const at::Tensor& targets, const at::Tensor& eff, const at::Tensor& info, int64_t V,
+                  std::optional<int64_t> ignore_index, const OptT& loss_mask, const OptT& doc_end, int64_t T,
+                  const OptT& denom, bool sum) {
+  check_cuda(targets, "targets", I64);
+  const int64_t N = targets.numel();
+  TORCH_CHECK(N <= INT32_MAX, "loss_targets: too many positions");
+  TORCH_CHECK(V >= 0 && V <= INT32_MAX, "loss_targets: vocab_size must fit 32 bits, got ", V);
+  check_cuda(eff, "eff", I64, N);
+  check_cuda(info, "info", I32, PDE_LI_WORDS);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(info.data_ptr()) % 16 == 0, "loss_targets: info must be 16-byte aligned");
+  PdeLossTargets a{};
+  a.targets = ptr<int64_t>(targets);
+  a.eff = ptr<int64_t>(eff);
+  a.info = ptr<int>(info);
+  if (loss_mask.has_value() && loss_mask->defined()) {
+    const at::Tensor& m = *loss_mask;
+    TORCH_CHECK(m.scalar_type() == U8 || m.scalar_type() == at::kBool, "loss_mask has dtype ", m.scalar_type(),
+                ", expected bool or uint8");
+    check_cuda(m, "loss_mask", m.scalar_type(), N);
+    TORCH_CHECK(m.numel() == N, "loss_mask has ", m.numel(), " elements, targets ", N);
+    a.loss_mask = reinterpret_cast<const uint8_t*>(m.data_ptr());
+  }
+  a.doc_end = optr<int>(doc_end, "doc_end", I32, N);
+  TORCH_CHECK(a.doc_end == nullptr || (T >= 1 && N % T == 0 && doc_end->numel() == N),
+              "loss_targets: doc_end must hold the targets' N positions in whole rows of T");
+  a.denom = optr<float>(denom, "denom", F32, 1);
+  TORCH_CHECK(a.denom == nullptr || !sum, "loss_targets: denom goes with the mean, not with the sum");
+  for (const OptT* o : {&loss_mask, &doc_end, &denom})
+    TORCH_CHECK(!o->has_value() || !(*o)->defined() || (*o)->device() == targets.device(),
+                "loss_targets: all tensors must be on the targets' device");
+  TORCH_CHECK(eff.device() == targets.device() && info.device() == targets.device(),
+              "loss_targets: all tensors must be on the targets' device");
+  a.ignore_index = ignore_index.value_or(0);
+  a.has_ignore = ignore_index.has_value();
+  a.N = (int)N;
+  a.T = (int)(a.doc_end ? T : 1);
+  a.V = (int)V;
+  a.mode = sum ? PDE_LOSS_SUM : PDE_LOSS_MEAN;
+  hip_check(pde_loss_targets(a, cur_stream()), "loss_targets");
 }
 
 // doc_start / doc_end (packed sequences, ops/transformer.py doc_bounds): int32 [B, T]; the position of
@@ -232,10 +283,12 @@ void colsum_bf16(const at::Tensor& x, const at::Tensor& part, const at::Tensor& 
             "colsum_bf16");
 }
 
-void sum_f32(const at::Tensor& x, const at::Tensor& out, double scale) {
+void sum_f32(const at::Tensor& x, const at::Tensor& out, double scale, const OptT& scale_dev) {
   check_cuda(x, "x", F32);
   check_cuda(out, "out", F32, 1);
-  hip_check(pde_sum_f32(ptr<float>(x), (int)x.numel(), ptr<float>(out), (float)scale, cur_stream()), "sum_f32");
+  const float* sd = optr<float>(scale_dev, "scale_dev", F32, 1);
+  TORCH_CHECK(sd == nullptr || scale_dev->device() == x.device(), "sum_f32: scale_dev must be on x's device");
+  hip_check(pde_sum_f32(ptr<float>(x), (int)x.numel(), ptr<float>(out), (float)scale, sd, cur_stream()), "sum_f32");
 }
 
 void token_batch(const at::Tensor& pool, const at::Tensor& rows, const at::Tensor& x, const at::Tensor& y) {
@@ -373,7 +426,11 @@ void register_transformer(pybind11::module& m) {
   m.def("gemm_set_dbg", [](int64_t d) { pde_gemm_set_dbg((int)d); });
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd", &gelu_bwd);
-  m.def("xent_bf16", &xent_bf16);
+  m.def("xent_bf16", &xent_bf16, py::arg("logits"), py::arg("tgt"), py::arg("V"), py::arg("scale"),
+        py::arg("loss_rows"), py::arg("write_grad"), py::arg("scale_dev") = py::none());
+  m.def("loss_targets", &loss_targets, py::arg("targets"), py::arg("eff"), py::arg("info"), py::arg("V"),
+        py::arg("ignore_index") = py::none(), py::arg("loss_mask") = py::none(), py::arg("doc_end") = py::none(),
+        py::arg("T") = 1, py::arg("denom") = py::none(), py::arg("sum") = false);
   m.def("embed_fwd", &embed_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe"), py::arg("out"), py::arg("T"), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0,
         py::arg("doc_start") = py::none());
   m.def("embed_bwd", &embed_bwd, py::arg("dX"), py::arg("idx"), py::arg("dwte"), py::arg("dwpe"), py::arg("acc"),
@@ -387,7 +444,8 @@ void register_transformer(pybind11::module& m) {
         py::arg("max_norm") = 1.0, py::arg("step_dev") = py::none(), py::arg("lr_table") = py::none());
   m.def("f32_to_bf16", &f32_to_bf16);
   m.def("scale_bf16", &scale_bf16);
-  m.def("sum_f32", &sum_f32, py::arg("x"), py::arg("out"), py::arg("scale") = 1.0);
+  m.def("sum_f32", &sum_f32, py::arg("x"), py::arg("out"), py::arg("scale") = 1.0,
+        py::arg("scale_dev") = py::none());
   m.def("token_batch", &token_batch);
   m.def("colsum_bf16_splits", &colsum_bf16_splits);
   m.def("colsum_bf16", &colsum_bf16);

@@ -154,8 +154,10 @@ hipError_t pde_ln_bwd(const void* dY, const void* X, const float* mean, const fl
                       PdeDrop drop, void* dD, hipStream_t st);
 hipError_t pde_gelu_fwd(const void* X, void* Y, int64_t n, hipStream_t st);
 hipError_t pde_gelu_bwd(const void* dY, const void* X, void* dX, int64_t n, hipStream_t st);
+// scale_dev (nullable, fp32 [1], pde_loss.h): the masked-loss instantiations -- the gradient scale is
+// scale * scale_dev[0] and a row whose target is outside [0, V) is zeroed without being read
 hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
-                         int write_grad, hipStream_t st);
+                         int write_grad, const float* scale_dev, hipStream_t st);
 // doc_start / doc_end (nullable, int32 [N]): packed sequences.  The forward reads wpe[t - doc_start[row]],
 // the backward sums dX into dwpe by that position, walking each row's documents through doc_end.
 hipError_t pde_embed_fwd(const int64_t* idx, const void* wte, const void* wpe, void* out, int N, int T, int C,
@@ -172,7 +174,8 @@ hipError_t pde_adamw_master(float* master, void* p16, const void* g16, float* m,
                             const float* lr_tab, int lr_len, hipStream_t st);
 hipError_t pde_f32_to_bf16(const float* x, void* y, int64_t n, hipStream_t st);
 hipError_t pde_scale_bf16(void* x, const float* s, int64_t n, hipStream_t st);   // x *= s[0], n % 8 == 0
-hipError_t pde_sum_f32(const float* x, int n, float* out, float scale, hipStream_t st);
+// out[0] = scale * (scale_dev ? scale_dev[0] : 1) * sum(x)
+hipError_t pde_sum_f32(const float* x, int n, float* out, float scale, const float* scale_dev, hipStream_t st);
 hipError_t pde_token_batch(const int64_t* pool, const int64_t* rows, int B, int T, int64_t* x, int64_t* y,
                            hipStream_t st);
 int pde_colsum_bf16_splits(int C);

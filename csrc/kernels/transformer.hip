@@ -9,6 +9,7 @@
 #include "pde_act.h"
 #include "pde_bf16.h"
 #include "pde_kernels.h"
+#include "pde_loss.h"
 #include "pde_lr.h"
 #include "pde_rng.h"
 
@@ -293,6 +294,17 @@ __global__ __launch_bounds__(256) void k_gelu_bwd(const uint4* __restrict__ dY, 
 // One block per row of logits [N, Vp] (bf16).  Pass 1: online max / sum-exp over the V real columns;
 // pass 2 overwrites the row IN PLACE with dlogits = (softmax - onehot) * scale (padding columns -> 0).
 // Target < 0 = ignore_index: loss 0, zero gradient.
+//
+// MASK (masked loss, ops.loss_targets): scale is multiplied by inv[0], the device-side 1 / denominator of
+// the batch (pde_loss.h), and a row whose target is outside [0, V) -- block-uniform: one scalar load -- leaves
+// before the row is read: no load, no exp, zeros to all Vp columns (write_grad) and loss 0, whatever the
+// row holds (NaN, inf).  The unmasked instantiations never touch inv and keep their instruction streams.
+__device__ __forceinline__ void xent_ignored_row(uint4* __restrict__ Lr, int nch, int tid,
+                                                 float* __restrict__ loss_rows, int row, int write_grad) {
+  if (tid == 0) loss_rows[row] = 0.f;
+  if (!write_grad) return;
+  for (int c = tid; c < nch; c += 256) Lr[c] = make_uint4(0u, 0u, 0u, 0u);
+}
 __device__ __forceinline__ void ms_combine(float& m, float& s, float m2, float s2) {
   const float mn = fmaxf(m, m2);
   s = (m == -INFINITY ? 0.f : s * __expf(m - mn)) + (m2 == -INFINITY ? 0.f : s2 * __expf(m2 - mn));
@@ -304,15 +316,19 @@ __device__ __forceinline__ void ms_combine(float& m, float& s, float m2, float s
 // softmax statistics and the dlogits come from registers -- the two-pass kernel below reads each
 // 100 KB row twice (the second time mostly from the last-level cache) for 3 row-sized transfers;
 // this one moves 2 (read + write).
-template <int NJ>
+template <int NJ, bool MASK>
 __global__ __launch_bounds__(256) void k_xent_bf16_reg(bf16_t* __restrict__ L, const int64_t* __restrict__ tgt,
                                                        int Vp, int V, float scale, float* __restrict__ loss_rows,
-                                                       int write_grad) {
+                                                       int write_grad, const float* __restrict__ inv) {
   __shared__ float shm[4], shs[4];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   uint4* Lr = reinterpret_cast<uint4*>(L + (size_t)row * Vp);
   const int nch = Vp >> 3;
   const int64_t t = tgt[row];
+  if constexpr (MASK) {
+    if (!(t >= 0 && t < V)) return xent_ignored_row(Lr, nch, tid, loss_rows, row, write_grad);
+    scale *= inv[0];
+  }
   const int t32 = (t >= 0 && t < V) ? (int)t : -1;
   uint4 q[NJ];
 #pragma unroll
@@ -401,16 +417,20 @@ __global__ __launch_bounds__(256) void k_xent_pad_fill(bf16_t* __restrict__ L, i
   L[row * Vp + V + (i - row * pad)] = (bf16_t)0xFF80u;   // -inf
 }
 
-template <int NJ>
+template <int NJ, bool MASK>
 __global__ __launch_bounds__(256, 2) void k_xent_bf16_reg2(bf16_t* __restrict__ L, const int64_t* __restrict__ tgt,
                                                            int Vp, int V, float scale, float* __restrict__ loss_rows,
-                                                           int write_grad) {
+                                                           int write_grad, const float* __restrict__ inv) {
   __shared__ float shr[4], shx;
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint4* Lr = reinterpret_cast<uint4*>(L + (size_t)row * Vp);
   const int nch = Vp >> 3;
   const int64_t t = tgt[row];
+  if constexpr (MASK) {   // ahead of the loads and of every fence below
+    if (!(t >= 0 && t < V)) return xent_ignored_row(Lr, nch, tid, loss_rows, row, write_grad);
+    scale *= inv[0];
+  }
   const bool valid = t >= 0 && t < V;
   const int t32 = valid ? (int)t : -1;
   const bool owner = valid && (t32 >> 3) % 256 == tid;   // this thread holds the target column
@@ -488,14 +508,19 @@ __global__ __launch_bounds__(256, 2) void k_xent_bf16_reg2(bf16_t* __restrict__ 
   if (owner) L[(size_t)row * Vp + t32] = f2bf((__expf(xt - lse) - 1.f) * sc);   // program order: after its chunk
 }
 
+template <bool MASK>
 __global__ __launch_bounds__(256) void k_xent_bf16(bf16_t* __restrict__ L, const int64_t* __restrict__ tgt, int Vp,
                                                    int V, float scale, float* __restrict__ loss_rows,
-                                                   int write_grad) {
+                                                   int write_grad, const float* __restrict__ inv) {
   __shared__ float shm[4], shs[4];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   uint4* Lr = reinterpret_cast<uint4*>(L + (size_t)row * Vp);
   const int nch = Vp >> 3;
   const int64_t t = tgt[row];
+  if constexpr (MASK) {
+    if (!(t >= 0 && t < V)) return xent_ignored_row(Lr, nch, tid, loss_rows, row, write_grad);
+    scale *= inv[0];
+  }
   const float xt = (t >= 0 && t < V) ? bf2f(L[(size_t)row * Vp + t]) : 0.f;
   float m = -INFINITY, s = 0.f;
   int c = tid;
@@ -559,6 +584,12 @@ __global__ __launch_bounds__(256) void k_xent_bf16(bf16_t* __restrict__ L, const
     Lr[c] = pack8(v);
   }
 }
+
+// the launcher's names of the two register-resident kernels at GPT-2's row width
+template <bool MASK>
+constexpr auto k_xent_bf16_reg25 = k_xent_bf16_reg<25, MASK>;
+template <bool MASK>
+constexpr auto k_xent_bf16_reg2_25 = k_xent_bf16_reg2<25, MASK>;
 
 // ---------------------------------------------------------------------------------- embeddings
 // DROP: embedding dropout applied while writing (element index = offset in the [N, C] output)
@@ -932,9 +963,11 @@ __global__ __launch_bounds__(256) void k_colsum_finish(const float* __restrict__
   if (w == 0 && blockIdx.x * 64 + lane < C) out[c] = f2bf(sh[0][lane] + sh[1][lane] + sh[2][lane] + sh[3][lane]);
 }
 
-// out[0] = sum(x[0..n)) (one 1024-thread block; n up to a few 1e5 -- loss rows)
+// out[0] = scale * sum(x[0..n)) (one 1024-thread block; n up to a few 1e5 -- loss rows).  DEV: scale is
+// multiplied by inv[0], a device value (the masked loss's 1 / denominator, pde_loss.h)
+template <bool DEV>
 __global__ __launch_bounds__(1024) void k_sum_f32(const float* __restrict__ x, int n, float* __restrict__ out,
-                                                  float scale) {
+                                                  float scale, const float* __restrict__ inv) {
   __shared__ float sh[16];
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 1024) s += x[i];
@@ -944,7 +977,55 @@ __global__ __launch_bounds__(1024) void k_sum_f32(const float* __restrict__ x, i
   if (threadIdx.x < 64) {
     float t = threadIdx.x < 16 ? sh[threadIdx.x] : 0.f;
     t = wave_sum(t);
+    if constexpr (DEV) scale *= inv[0];
     if (threadIdx.x == 0) out[0] = t * scale;
+  }
+}
+
+// Masked loss, the per-batch part that only the device knows (layout and meaning: pde_loss.h).  One
+// 1024-thread block like k_sum_f32: eff[i] = the target where it counts, else -1; integer counts, so the
+// result does not depend on the order of arrival; the info block leaves as one 16-byte vector store.
+__global__ __launch_bounds__(1024) void k_loss_targets(PdeLossTargets a) {
+  __shared__ int shc[16], sho[16];
+  int cnt = 0, oor = 0;
+  for (int i = threadIdx.x; i < a.N; i += 1024) {
+    const int64_t t = a.targets[i];
+    bool sel = a.loss_mask == nullptr || a.loss_mask[i] != 0;
+    if (a.doc_end != nullptr) {
+      const int tt = i % a.T;
+      sel = sel && !(tt < a.T - 1 && a.doc_end[i] == tt);
+    }
+    const bool live = sel && !(a.has_ignore && t == a.ignore_index);
+    const bool inr = t >= 0 && t < a.V;
+    cnt += live && inr;
+    oor += live && !inr;
+    a.eff[i] = live && inr ? t : -1;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    cnt += __shfl_xor(cnt, o, 64);
+    oor += __shfl_xor(oor, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    shc[threadIdx.x >> 6] = cnt;
+    sho[threadIdx.x >> 6] = oor;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    cnt = oor = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      cnt += shc[k];
+      oor += sho[k];
+    }
+    float inv = 1.f;
+    if (a.denom != nullptr) {
+      const float d = a.denom[0];
+      inv = d > 0.f ? __fdiv_rn(1.f, d) : 0.f;
+    } else if (a.mode == PDE_LOSS_MEAN) {
+      inv = __fdiv_rn(1.f, (float)max(cnt, 1));
+    }
+    *reinterpret_cast<int4*>(a.info) = make_int4(cnt, __float_as_int(inv), oor, 0);
   }
 }
 
@@ -1045,25 +1126,42 @@ hipError_t pde_gelu_bwd(const void* dY, const void* X, void* dX, int64_t n, hipS
   return hipGetLastError();
 }
 
+// scale_dev (nullable): the MASK instantiations (scale * scale_dev[0], ignored rows leave early)
 hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
-                         int write_grad, hipStream_t st) {
+                         int write_grad, const float* scale_dev, hipStream_t st) {
+  if (N == 0) return hipSuccess;
+#define XENT(K)                                                                                              \
+  do {                                                                                                       \
+    if (scale_dev)                                                                                           \
+      hipLaunchKernelGGL((K<true>), dim3(N), dim3(256), 0, st, (bf16_t*)logits, tgt, Vp, V, scale, loss_rows,   \
+                         write_grad, scale_dev);                                                             \
+    else                                                                                                     \
+      hipLaunchKernelGGL((K<false>), dim3(N), dim3(256), 0, st, (bf16_t*)logits, tgt, Vp, V, scale, loss_rows,  \
+                         write_grad, scale_dev);                                                             \
+  } while (0)
   if ((Vp >> 3) <= 256 * 25 && Vp >= 256 * 8 * 16) {   // wide rows (GPT-2 vocab): one read, one write
     const char* env = getenv("PDE_XENT_V");            // 1: the two-exp online-softmax kernel (A/B)
     // loss-only calls (write_grad = 0) keep the logits unmodified: the old kernel (no padding fill)
     if ((env && atoi(env) == 1) || Vp - V < 8 || !write_grad)
-      hipLaunchKernelGGL(k_xent_bf16_reg<25>, dim3(N), dim3(256), 0, st, (bf16_t*)logits, tgt, Vp, V, scale,
-                         loss_rows, write_grad);
+      XENT(k_xent_bf16_reg25);
     else {
       const int64_t np = (int64_t)N * (Vp - V);
       hipLaunchKernelGGL(k_xent_pad_fill, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, (bf16_t*)logits, N, Vp,
                          V);
-      hipLaunchKernelGGL(k_xent_bf16_reg2<25>, dim3(N), dim3(256), 0, st, (bf16_t*)logits, tgt, Vp, V, scale,
-                         loss_rows, write_grad);
+      XENT(k_xent_bf16_reg2_25);
     }
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_xent_bf16, dim3(N), dim3(256), 0, st, (bf16_t*)logits, tgt, Vp, V, scale, loss_rows,
-                     write_grad);
+  XENT(k_xent_bf16);
+#undef XENT
+  return hipGetLastError();
+}
+
+hipError_t pde_loss_targets(PdeLossTargets a, hipStream_t st) {
+  if (a.N < 0 || a.V < 0 || !a.targets || !a.eff || !a.info) return hipErrorInvalidValue;
+  if (a.doc_end && (a.T < 1 || a.N % a.T != 0)) return hipErrorInvalidValue;
+  if (a.denom && a.mode != PDE_LOSS_MEAN) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_loss_targets, dim3(1), dim3(1024), 0, st, a);
   return hipGetLastError();
 }
 
@@ -1150,8 +1248,9 @@ hipError_t pde_colsum_bf16(const void* x, int N, int C, float* part, void* out, 
   return hipGetLastError();
 }
 
-hipError_t pde_sum_f32(const float* x, int n, float* out, float scale, hipStream_t st) {
-  hipLaunchKernelGGL(k_sum_f32, dim3(1), dim3(1024), 0, st, x, n, out, scale);
+hipError_t pde_sum_f32(const float* x, int n, float* out, float scale, const float* scale_dev, hipStream_t st) {
+  if (scale_dev) hipLaunchKernelGGL(k_sum_f32<true>, dim3(1), dim3(1024), 0, st, x, n, out, scale, scale_dev);
+  else hipLaunchKernelGGL(k_sum_f32<false>, dim3(1), dim3(1024), 0, st, x, n, out, scale, scale_dev);
   return hipGetLastError();
 }
 

@@ -211,15 +211,29 @@ class GPT(tnn.Module):
         c = self.config
         return self.training and (c.embd_pdrop > 0.0 or c.attn_pdrop > 0.0 or c.resid_pdrop > 0.0)
 
-    def forward(self, idx, targets=None, doc_ids=None):
+    def forward(self, idx, targets=None, doc_ids=None, *, ignore_index=None, loss_mask=None, mask_doc_ends=False,
+                reduction="mean", denom=None):
         """Logits ``[B, T, V]``, or the mean cross-entropy against ``targets``.
 
         ``doc_ids`` (an integer ``[B, T]`` tensor on the model's device) marks packed rows: a document
         begins at ``t = 0`` and wherever ``doc_ids[b, t] != doc_ids[b, t - 1]``.  Every token then attends
         to its own document only and takes the learned position of its offset inside that document, so
-        each document is computed as if it stood alone at the start of a row.  The loss is still the mean
-        over all ``B * T`` targets, the one after each document's last token included.  ``None`` is the
-        call as it was."""
+        each document is computed as if it stood alone at the start of a row.  ``None`` is the call as it
+        was.
+
+        By default the loss is the mean over all ``B * T`` targets, the one after each document's last token
+        included.  The keywords select the masked loss (``ops.loss_targets``, ``ops.transformer.lm_head_loss``):
+        targets equal to ``ignore_index``, positions where ``loss_mask`` (bool / uint8 ``[B, T]``) is 0 and,
+        with ``mask_doc_ends=True`` (needs ``doc_ids``), the target after each document's last token do not
+        count, and the mean divides by the number of targets that do.  The target of the row's last position
+        ``t = T - 1`` is kept under ``mask_doc_ends``: whether its document goes on past the row cannot be
+        known from ``doc_ids``.  A batch without one valid target gives loss 0 and zero gradients, not NaN.
+        ``denom`` (an fp32 device scalar) replaces the count as the denominator, for a global mean over
+        data-parallel ranks or accumulated micro-batches; ``reduction`` is ``"mean"``, ``"sum"`` or
+        ``"none"`` (per-position losses, no gradient).  The valid count stays on the device, so a captured
+        step follows every batch."""
+        if mask_doc_ends and doc_ids is None:
+            raise ValueError("GPT.forward: mask_doc_ends=True needs doc_ids")
         t = self.transformer
         # computed once, on the device, and handed to the embedding and to every block
         bounds = None if doc_ids is None else T.doc_bounds(doc_ids)
@@ -244,7 +258,9 @@ class GPT(tnn.Module):
                                                   self.config.resid_pdrop, snap, 3 * len(t.h))[1]
         if targets is None:
             return T.lm_logits(x, t.wte.weight, self.config.vocab_size)
-        return T.lm_head_loss(x, t.wte.weight, targets, self.config.vocab_size)
+        return T.lm_head_loss(x, t.wte.weight, targets, self.config.vocab_size, ignore_index=ignore_index,
+                              loss_mask=loss_mask, doc_bounds=bounds if mask_doc_ends else None,
+                              mask_doc_ends=mask_doc_ends, reduction=reduction, denom=denom)
 
     # ------------------------------------------------------------------------------- generation
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, seed=None, generator=None,

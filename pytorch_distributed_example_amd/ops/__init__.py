@@ -10,7 +10,7 @@ import torch.nn.functional as F
 from .lenet_fused import LeNetFunction, lenet_forward, pack_conv2_weight  # noqa: F401
 from . import generic  # noqa: F401
 from . import transformer  # noqa: F401
-from .transformer import doc_bounds  # noqa: F401
+from .transformer import LossTargets, doc_bounds, loss_targets  # noqa: F401
 from . import rng  # noqa: F401
 from .rng import DeviceRNG, dropout_mask, effective_p  # noqa: F401
 from . import decode  # noqa: F401

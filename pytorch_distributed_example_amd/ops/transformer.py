@@ -14,6 +14,7 @@ the fused vocab softmax-cross-entropy that overwrites logits with dlogits in pla
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -277,6 +278,105 @@ def doc_bounds(doc_ids):
     return out[0], out[1]
 
 
+class LossTargets(NamedTuple):
+    """Result of ``loss_targets``.  ``count`` (int32), ``inv`` (fp32) and ``out_of_range`` (int32) are 0-d
+    views of one 16-byte info block (``csrc/include/pde_loss.h``)."""
+    targets: torch.Tensor
+    count: torch.Tensor
+    inv: torch.Tensor
+    out_of_range: torch.Tensor
+
+
+def loss_targets(targets, *, vocab_size: int, ignore_index=None, loss_mask=None, doc_bounds=None,
+                 mask_doc_ends=False, reduction="mean", denom=None):
+    """Which targets count towards a masked loss, and what the loss is multiplied by.
+
+    For position ``(b, t)`` of ``targets`` (row ``i = b * T + t``), with ``V = vocab_size``::
+
+        selected(i)  = (loss_mask is None or loss_mask[b, t] != 0)
+                       and not (mask_doc_ends and t < T - 1 and doc_end[b, t] == t)
+        valid(i)     = selected(i) and targets[i] != ignore_index and 0 <= targets[i] < V
+        count        = #valid
+        out_of_range = #{i: selected(i), targets[i] != ignore_index, not 0 <= targets[i] < V}
+        inv          = 1 / denom if denom > 0 else 0       (denom given)
+                       1 / max(count, 1)                   (reduction "mean")
+                       1                                   (reduction "sum" / "none"; no denom)
+
+    Returns ``LossTargets(targets, count, inv, out_of_range)``: the effective targets (int64, the input's
+    shape; the target where valid, else -1) and the three numbers as device scalars.  The loss is then
+    ``inv * sum over valid i of (lse_i - logit_i[target_i])``.
+
+    * No valid target: ``count = 0``, ``inv = 1``, so the loss is 0 and every gradient exactly zero
+      (``F.cross_entropy`` gives NaN): a batch of pure padding does not poison a run.
+    * ``mask_doc_ends`` (needs ``doc_bounds``, the pair of ``doc_bounds(doc_ids)``) drops the target after
+      each document's last token, which belongs to the next document.  The target of the last position
+      ``t = T - 1`` is kept: whether its document goes on past the row cannot be known from ``doc_ids``
+      (exclude it with ``loss_mask`` or ``ignore_index`` where it does not).
+    * Targets outside ``[0, V)`` cannot raise (that needs a host read): they are ignored and counted in
+      ``out_of_range``, for a caller to read when debugging.
+    * ``loss_mask`` is a bool or uint8 tensor of the targets' shape; ``denom`` an fp32 scalar tensor (or a
+      number) on the targets' device, e.g. the all-reduced ``count`` of a data-parallel step.
+
+    GPU tensors run one kernel on the current stream with no host read, so this can sit inside a captured
+    step; CPU tensors give the same values from torch ops."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"loss_targets: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+    if denom is not None and reduction != "mean":
+        raise ValueError(f"loss_targets: denom replaces the mean's denominator; it cannot go with "
+                         f"reduction={reduction!r}")
+    if mask_doc_ends and doc_bounds is None:
+        raise ValueError("loss_targets: mask_doc_ends=True needs doc_bounds (the pair of ops.doc_bounds(doc_ids))")
+    if targets.is_floating_point() or targets.dtype == torch.bool:
+        raise ValueError(f"loss_targets: targets must be an integer tensor, got {targets.dtype}")
+    dev = targets.device
+    tg = _c(targets.reshape(-1).long())
+    N = tg.numel()
+    mask = de = None
+    T = 1
+    if loss_mask is not None:
+        if tuple(loss_mask.shape) != tuple(targets.shape) or loss_mask.device != dev:
+            raise ValueError(f"loss_targets: loss_mask must have the targets' shape and device (got "
+                             f"{tuple(loss_mask.shape)} on {loss_mask.device})")
+        mask = loss_mask if loss_mask.dtype in (torch.bool, torch.uint8) else loss_mask != 0
+        mask = _c(mask.reshape(-1))
+    if mask_doc_ends:
+        de = doc_bounds[1]
+        if de.dim() != 2 or de.numel() != N:
+            raise ValueError(f"loss_targets: doc_bounds must cover the targets ({tuple(de.shape)} against "
+                             f"{tuple(targets.shape)})")
+        de = _check_bounds(doc_bounds, de.shape[0], de.shape[1], dev, "loss_targets")[1]
+        T = de.shape[1]
+    if denom is not None:
+        denom = torch.as_tensor(denom, dtype=torch.float32, device=dev).reshape(-1)
+        if denom.numel() != 1:
+            raise ValueError("loss_targets: denom must hold one value")
+    info = torch.empty(4, device=dev, dtype=torch.int32)
+    if _gpu(targets):
+        eff = torch.empty_like(tg)
+        kernels().loss_targets(tg, eff, info, int(vocab_size), ignore_index, mask, de, T, denom,
+                               reduction != "mean")
+    else:
+        sel = torch.ones(N, dtype=torch.bool) if mask is None else mask != 0
+        if de is not None:
+            t = torch.arange(T, dtype=torch.int32)
+            sel = sel & ~((de == t) & (t < T - 1)).reshape(-1)
+        live = sel if ignore_index is None else sel & (tg != ignore_index)
+        inr = (tg >= 0) & (tg < vocab_size)
+        valid = live & inr
+        eff = torch.where(valid, tg, tg.new_full((), -1))
+        info[0] = valid.sum()
+        info[2] = (live & ~inr).sum()
+        info[3] = 0
+        if denom is not None:
+            inv = torch.where(denom > 0, 1.0 / denom, denom.new_zeros(()))
+        elif reduction == "mean":
+            inv = 1.0 / info[0:1].clamp(min=1).float()
+        else:
+            inv = torch.ones(1)
+        info[1:2].view(torch.float32).copy_(inv)
+    return LossTargets(eff.view(targets.shape), info[0], info[1:2].view(torch.float32)[0], info[2])
+
+
 def doc_allowed(doc_start):
     """bool ``[B, 1, T, T]`` (query, key): ``doc_start[b, q] <= k <= q``, the mask the kernels apply."""
     T = doc_start.shape[1]
@@ -484,13 +584,14 @@ class LMHeadLossFn(torch.autograd.Function):
     """mean cross-entropy of logits = h @ W^T over the first V columns of W ([Vp, C], padded vocab).
 
     Forward runs the GEMM and the fused softmax-CE kernel, which overwrites the logits buffer with
-    dlogits = (softmax - onehot) / N; backward is two GEMMs from that buffer with the incoming loss
+    dlogits = (softmax - onehot) / N (masked loss: times ``inv[0]``, a device value, and exact zeros in
+    rows that do not count); backward is two GEMMs from that buffer with the incoming loss
     gradient applied in their epilogues (a device scalar: no host read, no extra kernel, graph-safe,
     and the saved dlogits stay unscaled, so a retained graph can run backward again).  With W tied to
     the embedding of the same forward pass, dW is left for the embedding backward to accumulate into."""
 
     @staticmethod
-    def forward(ctx, h, w, targets, V):
+    def forward(ctx, h, w, targets, V, inv=None):
         C = h.shape[-1]
         h2 = _c(h.reshape(-1, C))
         N = h2.shape[0]
@@ -499,9 +600,13 @@ class LMHeadLossFn(torch.autograd.Function):
         # [N, Vp] bf16 logits on the own persistent GEMM; 1.65 GB at GPT-2 shapes, stored non-temporally
         # (read back once, by the cross-entropy right after) so they do not evict the operand tiles
         logits = G.fprop(h2, w, nt_out=True)
-        kernels().xent_bf16(logits, tg, V, 1.0 / N, rows, True)
         tot = torch.empty(1, device=h.device, dtype=torch.float32)
-        kernels().sum_f32(rows, tot, 1.0 / N)               # mean loss, no separate divide
+        if inv is None:
+            kernels().xent_bf16(logits, tg, V, 1.0 / N, rows, True)
+            kernels().sum_f32(rows, tot, 1.0 / N)               # mean loss, no separate divide
+        else:   # masked loss: targets are loss_targets' effective ones, inv its device-side 1 / denominator
+            kernels().xent_bf16(logits, tg, V, 1.0, rows, True, scale_dev=inv)
+            kernels().sum_f32(rows, tot, 1.0, scale_dev=inv)
         ctx.save_for_backward(h2, w, logits)
         ctx.hshape = h.shape
         ctx.tied = getattr(w, "_pde_tied_slot", None)
@@ -521,14 +626,54 @@ class LMHeadLossFn(torch.autograd.Function):
         dw, _ = G.wgrad(dlogits, h2, dw=_grad_out(w), scale=gs)   # [Vp, C]
         if ctx.tied is not None:
             ctx.tied["dw"] = dw                              # the tied embedding adds its part in place
-        return dh.reshape(ctx.hshape), dw, None, None
+        return dh.reshape(ctx.hshape), dw, None, None, None
 
 
-def lm_head_loss(h, w, targets, V: int):
+def lm_head_loss(h, w, targets, V: int, *, ignore_index=None, loss_mask=None, doc_bounds=None, mask_doc_ends=False,
+                 reduction="mean", denom=None):
+    """Cross-entropy of ``logits = h @ w[:V]^T`` against ``targets``.
+
+    With every keyword at its default this is the call as it was: the mean over all ``N`` targets (on the
+    GPU a negative target gives loss 0 and still counts in ``N``).  Any other value selects the masked loss
+    of ``loss_targets`` (the definition is there): ``loss = inv * sum over valid rows of (lse - logit[target])``,
+    where a row is valid if it is selected by ``loss_mask`` / ``mask_doc_ends``, its target is not
+    ``ignore_index`` and lies in ``[0, V)``.  An invalid row contributes exact zeros to the loss and to every
+    gradient whatever its logits hold, and a batch without one valid target gives loss 0 and zero gradients
+    (``F.cross_entropy`` gives NaN there).  ``denom`` (an fp32 device scalar) replaces the valid count as the
+    mean's denominator: the total count of a data-parallel or accumulated step.  On the GPU the count never
+    reaches the host, so a captured step follows the batch.
+
+    ``reduction``: ``"mean"``, ``"sum"`` (no ``denom``), or ``"none"``: the per-position losses, fp32 in the
+    input's leading shape, 0 where not valid; no gradient (``NotImplementedError`` if one is asked for)."""
+    if (ignore_index is None and loss_mask is None and doc_bounds is None and not mask_doc_ends
+            and reduction == "mean" and denom is None):
+        if _gpu(h):
+            return LMHeadLossFn.apply(h, w, targets, V)
+        logits = torch.matmul(h, w.t())[..., :V].float()
+        return F.cross_entropy(logits.reshape(-1, V), targets.reshape(-1))
+    lt = loss_targets(targets, vocab_size=V, ignore_index=ignore_index, loss_mask=loss_mask, doc_bounds=doc_bounds,
+                      mask_doc_ends=mask_doc_ends, reduction=reduction, denom=denom)
+    if reduction == "none" and torch.is_grad_enabled() and (h.requires_grad or w.requires_grad):
+        raise NotImplementedError("lm_head_loss: reduction='none' has no backward; call it under torch.no_grad()")
     if _gpu(h):
-        return LMHeadLossFn.apply(h, w, targets, V)
-    logits = torch.matmul(h, w.t())[..., :V].float()
-    return F.cross_entropy(logits.reshape(-1, V), targets.reshape(-1))
+        if reduction != "none":
+            return LMHeadLossFn.apply(h, w, lt.targets, V, lt.inv)
+        C = h.shape[-1]
+        h2 = _c(h.reshape(-1, C))
+        rows = torch.empty(h2.shape[0], device=h.device, dtype=torch.float32)
+        # loss only (write_grad = 0): the logits stay as they are, ignored rows are not read
+        kernels().xent_bf16(G.fprop(h2, w, nt_out=True), _c(lt.targets.reshape(-1)), V, 1.0, rows, False,
+                            scale_dev=lt.inv)
+        return rows.view(h.shape[:-1])
+    eff = lt.targets.reshape(-1)
+    valid = eff >= 0
+    logits = torch.matmul(h, w.t())[..., :V].float().reshape(-1, V)
+    # an ignored row counts as zeros whatever it holds: taken out before the softmax, so NaN cannot leak
+    logits = torch.where(valid[:, None], logits, logits.new_zeros(()))
+    rows = F.cross_entropy(logits, eff, ignore_index=-1, reduction="none")
+    if reduction == "none":
+        return rows.view(h.shape[:-1])
+    return rows.sum() * lt.inv
 
 
 def lm_logits(h, w, V: int):
