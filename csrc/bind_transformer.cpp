@@ -118,9 +118,12 @@ void gelu_bwd(const at::Tensor& dY, const at::Tensor& X, const at::Tensor& dX) {
   hip_check(pde_gelu_bwd(dY.data_ptr(), X.data_ptr(), dX.data_ptr(), X.numel(), cur_stream()), "gelu_bwd");
 }
 
-// scale_dev (fp32 [1], e.g. the inv word of loss_targets' info block): the masked-loss kernels
+// scale_dev (fp32 [1], e.g. the inv word of loss_targets' info block): the masked-loss kernels.
+// label_smoothing / z_loss / loss_weights (fp32 [N]): any of them away from 0 / 0 / None selects the smoothed and
+// weighted kernels (PdeXentSmooth in pde_kernels.h), which need scale_dev.
 void xent_bf16(const at::Tensor& logits, const at::Tensor& tgt, int64_t V, double scale, const at::Tensor& loss_rows,
-               bool write_grad, const OptT& scale_dev) {
+               bool write_grad, const OptT& scale_dev, double label_smoothing, double z_loss,
+               const OptT& loss_weights) {
   check_cuda(logits, "logits", BF16);
   TORCH_CHECK(logits.dim() == 2 && logits.size(1) % 8 == 0, "logits must be [N, Vp] with Vp % 8 == 0");
   const int64_t N = logits.size(0), Vp = logits.size(1);
@@ -132,8 +135,23 @@ void xent_bf16(const at::Tensor& logits, const at::Tensor& tgt, int64_t V, doubl
   TORCH_CHECK(tgt.device() == logits.device() && loss_rows.device() == logits.device() &&
                   (sd == nullptr || scale_dev->device() == logits.device()),
               "xent_bf16: all tensors must be on the logits' device");
-  hip_check(pde_xent_bf16(logits.data_ptr(), ptr<int64_t>(tgt), (int)N, (int)Vp, (int)V, (float)scale,
-                          ptr<float>(loss_rows), write_grad, sd, cur_stream()),
+  const float* wp = optr<float>(loss_weights, "loss_weights", F32, N);
+  if (wp == nullptr && label_smoothing == 0.0 && z_loss == 0.0) {
+    hip_check(pde_xent_bf16(logits.data_ptr(), ptr<int64_t>(tgt), (int)N, (int)Vp, (int)V, (float)scale,
+                            ptr<float>(loss_rows), write_grad, sd, cur_stream()),
+              "xent_bf16");
+    return;
+  }
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "xent_bf16: label_smoothing must be in [0, 1), got ",
+              label_smoothing);
+  TORCH_CHECK(z_loss >= 0.0 && std::isfinite(z_loss), "xent_bf16: z_loss must be finite and >= 0, got ", z_loss);
+  TORCH_CHECK(sd != nullptr, "xent_bf16: the smoothed and weighted loss needs scale_dev");
+  TORCH_CHECK(V >= 1, "xent_bf16: the smoothed and weighted loss needs V >= 1");
+  TORCH_CHECK(wp == nullptr || (loss_weights->numel() == N && loss_weights->device() == logits.device()),
+              "xent_bf16: loss_weights must hold N floats on the logits' device");
+  const PdeXentSmooth sm{wp, (float)(1.0 - label_smoothing), (float)(label_smoothing / (double)V), (float)z_loss};
+  hip_check(pde_xent_bf16_smooth(logits.data_ptr(), ptr<int64_t>(tgt), (int)N, (int)Vp, (int)V, (float)scale,
+                                 ptr<float>(loss_rows), write_grad, sd, sm, cur_stream()),
             "xent_bf16");
 }
 
@@ -427,7 +445,8 @@ void register_transformer(pybind11::module& m) {
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd", &gelu_bwd);
   m.def("xent_bf16", &xent_bf16, py::arg("logits"), py::arg("tgt"), py::arg("V"), py::arg("scale"),
-        py::arg("loss_rows"), py::arg("write_grad"), py::arg("scale_dev") = py::none());
+        py::arg("loss_rows"), py::arg("write_grad"), py::arg("scale_dev") = py::none(),
+        py::arg("label_smoothing") = 0.0, py::arg("z_loss") = 0.0, py::arg("loss_weights") = py::none());
   m.def("loss_targets", &loss_targets, py::arg("targets"), py::arg("eff"), py::arg("info"), py::arg("V"),
         py::arg("ignore_index") = py::none(), py::arg("loss_mask") = py::none(), py::arg("doc_end") = py::none(),
         py::arg("T") = 1, py::arg("denom") = py::none(), py::arg("sum") = false);

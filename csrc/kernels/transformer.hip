@@ -299,11 +299,30 @@ __global__ __launch_bounds__(256) void k_gelu_bwd(const uint4* __restrict__ dY, 
 // the batch (pde_loss.h), and a row whose target is outside [0, V) -- block-uniform: one scalar load -- leaves
 // before the row is read: no load, no exp, zeros to all Vp columns (write_grad) and loss 0, whatever the
 // row holds (NaN, inf).  The unmasked instantiations never touch inv and keep their instruction streams.
+//
+// SMOOTH (label smoothing, z-loss, per-row weights; PdeXentSmooth in pde_kernels.h) implies MASK's exit and inv,
+// and adds one row sum -- the logits of the columns < V, selected by index, folded into the pass that already
+// walks the register-resident row -- one block-uniform weight load after the exit (the weight of an ignored
+// row is never read), and a changed epilogue:
+//   loss = w (lse - keep x_t - spread sum x + z lse^2),   dlogits = w inv ((1 + 2 z lse) p - keep [v == t] - spread)
+// With keep = 1, spread = 0, z = 0, w = 1 every added operation is exact (1 * x, x - 0, x + 0), so the bits are
+// MASK's.  The unmasked and MASK instantiations never touch sm and keep their instruction streams.
 __device__ __forceinline__ void xent_ignored_row(uint4* __restrict__ Lr, int nch, int tid,
                                                  float* __restrict__ loss_rows, int row, int write_grad) {
   if (tid == 0) loss_rows[row] = 0.f;
   if (!write_grad) return;
   for (int c = tid; c < nch; c += 256) Lr[c] = make_uint4(0u, 0u, 0u, 0u);
+}
+// the weight of a row that counts, loaded (scalar) ahead of the row's own loads
+__device__ __forceinline__ float xent_row_weight(const PdeXentSmooth& sm, int row) {
+  // nothing writes the weights while the kernel runs: read through the constant address space, which makes
+  // the block-uniform load a scalar one (a pointer inside a by-value struct carries no such promise)
+  typedef const __attribute__((address_space(4))) float* cptr;
+  return sm.w ? ((cptr)(uintptr_t)sm.w)[row] : 1.f;
+}
+// w (lse - keep x_t - spread sum x + z lse^2): no exp of its own
+__device__ __forceinline__ float xent_smooth_loss(const PdeXentSmooth& sm, float wr, float lse, float xt, float sx) {
+  return wr * (((lse - sm.keep * xt) - sm.spread * sx) + sm.z * lse * lse);
 }
 __device__ __forceinline__ void ms_combine(float& m, float& s, float m2, float s2) {
   const float mn = fmaxf(m, m2);
@@ -316,18 +335,24 @@ __device__ __forceinline__ void ms_combine(float& m, float& s, float m2, float s
 // softmax statistics and the dlogits come from registers -- the two-pass kernel below reads each
 // 100 KB row twice (the second time mostly from the last-level cache) for 3 row-sized transfers;
 // this one moves 2 (read + write).
-template <int NJ, bool MASK>
+template <int NJ, bool MASK, bool SMOOTH>
 __global__ __launch_bounds__(256) void k_xent_bf16_reg(bf16_t* __restrict__ L, const int64_t* __restrict__ tgt,
                                                        int Vp, int V, float scale, float* __restrict__ loss_rows,
-                                                       int write_grad, const float* __restrict__ inv) {
+                                                       int write_grad, const float* __restrict__ inv,
+                                                       PdeXentSmooth sm) {
   __shared__ float shm[4], shs[4];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   uint4* Lr = reinterpret_cast<uint4*>(L + (size_t)row * Vp);
   const int nch = Vp >> 3;
   const int64_t t = tgt[row];
-  if constexpr (MASK) {
+  if constexpr (MASK || SMOOTH) {
     if (!(t >= 0 && t < V)) return xent_ignored_row(Lr, nch, tid, loss_rows, row, write_grad);
     scale *= inv[0];
+  }
+  float wr = 1.f, sx = 0.f;
+  if constexpr (SMOOTH) {
+    wr = xent_row_weight(sm, row);
+    scale *= wr;
   }
   const int t32 = (t >= 0 && t < V) ? (int)t : -1;
   uint4 q[NJ];
@@ -350,6 +375,7 @@ __global__ __launch_bounds__(256) void k_xent_bf16_reg(bf16_t* __restrict__ L, c
     for (int e = 0; e < 8; ++e) {
       bs += col0 + e < V ? __expf(v[e] - bm) : 0.f;
       xt += col0 + e == t32 ? v[e] : 0.f;
+      if constexpr (SMOOTH) sx += col0 + e < V ? v[e] : 0.f;
     }
     ms_combine(m, s, bm, bs);
   }
@@ -358,12 +384,14 @@ __global__ __launch_bounds__(256) void k_xent_bf16_reg(bf16_t* __restrict__ L, c
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
     ms_combine(m, s, m2, s2);
     xt += __shfl_xor(xt, o, 64);
+    if constexpr (SMOOTH) sx += __shfl_xor(sx, o, 64);
   }
-  __shared__ float shx[4];
+  __shared__ float shx[4], shq[SMOOTH ? 4 : 1];
   if (lane == 0) {
     shm[w] = m;
     shs[w] = s;
     shx[w] = xt;
+    if constexpr (SMOOTH) shq[w] = sx;
   }
   __syncthreads();
   m = shm[0];
@@ -373,9 +401,15 @@ __global__ __launch_bounds__(256) void k_xent_bf16_reg(bf16_t* __restrict__ L, c
   xt = (shx[0] + shx[1]) + (shx[2] + shx[3]);
   const float lse = m + __logf(s);
   const bool valid = t >= 0 && t < V;
-  if (tid == 0) loss_rows[row] = valid ? lse - xt : 0.f;
+  if constexpr (SMOOTH) {
+    if (tid == 0)
+      loss_rows[row] = xent_smooth_loss(sm, wr, lse, xt, (shq[0] + shq[1]) + (shq[2] + shq[3]));
+  } else {
+    if (tid == 0) loss_rows[row] = valid ? lse - xt : 0.f;
+  }
   if (!write_grad) return;
   const float sc = valid ? scale : 0.f;
+  const float kf = SMOOTH ? fmaf(2.f * sm.z, lse, 1.f) : 1.f;   // 1 + 2 z lse
   // opaque to the optimiser: the pass-1 unpacked floats are re-derived from the packed words
   // (2 VGPRs per 4 values) instead of being kept live across the reduction (248 -> fewer VGPRs)
 #pragma unroll
@@ -389,8 +423,13 @@ __global__ __launch_bounds__(256) void k_xent_bf16_reg(bf16_t* __restrict__ L, c
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const int col = c * 8 + e;
-        const float p = col < V ? __expf(v[e] - lse) : 0.f;
-        v[e] = (p - (col == t32 ? 1.f : 0.f)) * sc;
+        if constexpr (SMOOTH) {
+          const float g = ((kf * __expf(v[e] - lse) - (col == t32 ? sm.keep : 0.f)) - sm.spread) * sc;
+          v[e] = col < V ? g : 0.f;
+        } else {
+          const float p = col < V ? __expf(v[e] - lse) : 0.f;
+          v[e] = (p - (col == t32 ? 1.f : 0.f)) * sc;
+        }
       }
       Lr[c] = pack8(v);
     }
@@ -409,6 +448,10 @@ __global__ __launch_bounds__(256) void k_xent_bf16_reg(bf16_t* __restrict__ L, c
 // the fp16 copy).  No per-element masking: k_xent_pad_fill first sets the vocab padding [V, Vp) of
 // every row to -inf (exp -> 0, ignored by the max), and the launcher requires Vp - V >= 8 so the
 // clamped duplicate loads of lanes past the row end are copies of a fully padded chunk.
+// SMOOTH: the row sum of the logits joins pass 0 and the gradient is q * f - spread * sc.  Neither the -inf
+// padding nor a clamped duplicate may enter the sum, and the constant would make the padding columns
+// non-zero, so both select by the column index -- but only in the chunk slots j >= (V / 8) / 256 (a uniform
+// scalar branch: at GPT-2's width the last slot alone); every slot below holds real columns only.
 __global__ __launch_bounds__(256) void k_xent_pad_fill(bf16_t* __restrict__ L, int N, int Vp, int V) {
   const int pad = Vp - V;
   const int64_t i = blockIdx.x * 256ll + threadIdx.x;
@@ -417,20 +460,27 @@ __global__ __launch_bounds__(256) void k_xent_pad_fill(bf16_t* __restrict__ L, i
   L[row * Vp + V + (i - row * pad)] = (bf16_t)0xFF80u;   // -inf
 }
 
-template <int NJ, bool MASK>
+template <int NJ, bool MASK, bool SMOOTH>
 __global__ __launch_bounds__(256, 2) void k_xent_bf16_reg2(bf16_t* __restrict__ L, const int64_t* __restrict__ tgt,
                                                            int Vp, int V, float scale, float* __restrict__ loss_rows,
-                                                           int write_grad, const float* __restrict__ inv) {
-  __shared__ float shr[4], shx;
+                                                           int write_grad, const float* __restrict__ inv,
+                                                           PdeXentSmooth sm) {
+  __shared__ float shr[4], shx, shq[SMOOTH ? 4 : 1];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint4* Lr = reinterpret_cast<uint4*>(L + (size_t)row * Vp);
   const int nch = Vp >> 3;
   const int64_t t = tgt[row];
-  if constexpr (MASK) {   // ahead of the loads and of every fence below
+  if constexpr (MASK || SMOOTH) {   // ahead of the loads and of every fence below
     if (!(t >= 0 && t < V)) return xent_ignored_row(Lr, nch, tid, loss_rows, row, write_grad);
     scale *= inv[0];
   }
+  float wr = 1.f, sx = 0.f;
+  if constexpr (SMOOTH) {
+    wr = xent_row_weight(sm, row);
+    scale *= wr;
+  }
+  const int jfull = (V >> 3) >> 8;   // chunk slots below it hold columns < V only, in every thread
   const bool valid = t >= 0 && t < V;
   const int t32 = valid ? (int)t : -1;
   const bool owner = valid && (t32 >> 3) % 256 == tid;   // this thread holds the target column
@@ -447,11 +497,35 @@ __global__ __launch_bounds__(256, 2) void k_xent_bf16_reg2(bf16_t* __restrict__ 
     unpack8(q[j], v);
 #pragma unroll
     for (int e = 0; e < 8; ++e) mx = fmaxf(mx, v[e]);
+    if constexpr (SMOOTH) {
+      if (j < jfull) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sx += v[e];
+      } else {   // by the unclamped index: not the -inf padding, not a duplicate chunk
+        int tid0 = tid;                      // opaque copy: recomputed here, not kept live from the loads
+        asm volatile("" : "+v"(tid0));
+        const int col0 = (tid0 + 256 * j) * 8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sx += col0 + e < V ? v[e] : 0.f;
+      }
+    }
     __builtin_amdgcn_sched_barrier(0);               // chunk by chunk: the row stays packed (q only)
   }
+  // opaque: pass 1 unpacks the words again; pass 0's floats do not stay live across its branches (they would
+  // not fit next to the row)
+  if constexpr (SMOOTH) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  if (lane == 0) shr[w] = mx;
+    for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(q[j].x), "+v"(q[j].y), "+v"(q[j].z), "+v"(q[j].w));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if constexpr (SMOOTH) sx += __shfl_xor(sx, o, 64);
+  }
+  if (lane == 0) {
+    shr[w] = mx;
+    if constexpr (SMOOTH) shq[w] = sx;                 // read once more, by thread 0 for the loss
+  }
   float xt = 0.f;
   if (owner) {   // the target logit: one (L2-hit) load -- selecting it from q would index q dynamically
     xt = bf2f(L[(size_t)row * Vp + t32]);                // and push the whole row array to scratch
@@ -486,9 +560,16 @@ __global__ __launch_bounds__(256, 2) void k_xent_bf16_reg2(bf16_t* __restrict__ 
   __syncthreads();
   const float s = (shr[0] + shr[1]) + (shr[2] + shr[3]);        // 2^15 x the softmax denominator
   const float lse = M + __logf(s) - 10.397207708399179f;         // - 15 ln 2
-  if (tid == 0) loss_rows[row] = valid ? lse - shx : 0.f;
+  if constexpr (SMOOTH) {
+    if (tid == 0)
+      loss_rows[row] = xent_smooth_loss(sm, wr, lse, shx, (shq[0] + shq[1]) + (shq[2] + shq[3]));
+  } else {
+    if (tid == 0) loss_rows[row] = valid ? lse - shx : 0.f;
+  }
   if (!write_grad) return;
-  const float sc = valid ? scale : 0.f, f = sc / s;
+  const float kf = SMOOTH ? fmaf(2.f * sm.z, lse, 1.f) : 1.f;   // 1 + 2 z lse
+  const float sc = valid ? scale : 0.f, f = SMOOTH ? kf * sc / s : sc / s;
+  const float ssc = SMOOTH ? sm.spread * sc : 0.f;
   int tid2 = tid;                                    // opaque copy: the store offsets are recomputed
   asm volatile("" : "+v"(tid2));                     // here, not kept live (spilled) from the loads
 #pragma unroll
@@ -499,27 +580,48 @@ __global__ __launch_bounds__(256, 2) void k_xent_bf16_reg2(bf16_t* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const auto hv = __builtin_bit_cast(__fp16 __attribute__((ext_vector_type(2))), hw[k]);
-      g[2 * k] = (float)hv[0] * f;
-      g[2 * k + 1] = (float)hv[1] * f;
+      if constexpr (SMOOTH) {
+        g[2 * k] = (float)hv[0] * f - ssc;
+        g[2 * k + 1] = (float)hv[1] * f - ssc;
+      } else {
+        g[2 * k] = (float)hv[0] * f;
+        g[2 * k + 1] = (float)hv[1] * f;
+      }
+    }
+    if constexpr (SMOOTH) {
+      if (j >= jfull) {   // a chunk that may reach past V: its padding columns stay exact zeros
+#pragma unroll
+        for (int e = 0; e < 8; ++e) g[e] = c * 8 + e < V ? g[e] : 0.f;
+      }
     }
     if (c < nch) Lr[c] = pack8(g);
     __builtin_amdgcn_sched_barrier(0);
   }
-  if (owner) L[(size_t)row * Vp + t32] = f2bf((__expf(xt - lse) - 1.f) * sc);   // program order: after its chunk
+  // program order: after its chunk
+  if constexpr (SMOOTH) {
+    if (owner) L[(size_t)row * Vp + t32] = f2bf(((kf * __expf(xt - lse) - sm.keep) - sm.spread) * sc);
+  } else {
+    if (owner) L[(size_t)row * Vp + t32] = f2bf((__expf(xt - lse) - 1.f) * sc);
+  }
 }
 
-template <bool MASK>
+template <bool MASK, bool SMOOTH>
 __global__ __launch_bounds__(256) void k_xent_bf16(bf16_t* __restrict__ L, const int64_t* __restrict__ tgt, int Vp,
                                                    int V, float scale, float* __restrict__ loss_rows,
-                                                   int write_grad, const float* __restrict__ inv) {
-  __shared__ float shm[4], shs[4];
+                                                   int write_grad, const float* __restrict__ inv, PdeXentSmooth sm) {
+  __shared__ float shm[4], shs[4], shq[SMOOTH ? 4 : 1];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   uint4* Lr = reinterpret_cast<uint4*>(L + (size_t)row * Vp);
   const int nch = Vp >> 3;
   const int64_t t = tgt[row];
-  if constexpr (MASK) {
+  if constexpr (MASK || SMOOTH) {
     if (!(t >= 0 && t < V)) return xent_ignored_row(Lr, nch, tid, loss_rows, row, write_grad);
     scale *= inv[0];
+  }
+  float wr = 1.f, sx = 0.f;
+  if constexpr (SMOOTH) {
+    wr = xent_row_weight(sm, row);
+    scale *= wr;
   }
   const float xt = (t >= 0 && t < V) ? bf2f(L[(size_t)row * Vp + t]) : 0.f;
   float m = -INFINITY, s = 0.f;
@@ -536,7 +638,10 @@ __global__ __launch_bounds__(256) void k_xent_bf16(bf16_t* __restrict__ L, const
       for (int e = 0; e < 8; ++e) bm = fmaxf(bm, col0 + e < V ? v[e] : -INFINITY);
       float bs = 0.f;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) bs += col0 + e < V ? __expf(v[e] - bm) : 0.f;
+      for (int e = 0; e < 8; ++e) {
+        bs += col0 + e < V ? __expf(v[e] - bm) : 0.f;
+        if constexpr (SMOOTH) sx += col0 + e < V ? v[e] : 0.f;
+      }
       ms_combine(m, s, bm, bs);
     }
   }
@@ -549,17 +654,22 @@ __global__ __launch_bounds__(256) void k_xent_bf16(bf16_t* __restrict__ L, const
     for (int e = 0; e < 8; ++e) bm = fmaxf(bm, col0 + e < V ? v[e] : -INFINITY);
     float bs = 0.f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) bs += col0 + e < V ? __expf(v[e] - bm) : 0.f;
+    for (int e = 0; e < 8; ++e) {
+      bs += col0 + e < V ? __expf(v[e] - bm) : 0.f;
+      if constexpr (SMOOTH) sx += col0 + e < V ? v[e] : 0.f;
+    }
     ms_combine(m, s, bm, bs);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
     ms_combine(m, s, m2, s2);
+    if constexpr (SMOOTH) sx += __shfl_xor(sx, o, 64);
   }
   if (lane == 0) {
     shm[w] = m;
     shs[w] = s;
+    if constexpr (SMOOTH) shq[w] = sx;
   }
   __syncthreads();
   m = shm[0];
@@ -568,9 +678,15 @@ __global__ __launch_bounds__(256) void k_xent_bf16(bf16_t* __restrict__ L, const
   for (int k = 1; k < 4; ++k) ms_combine(m, s, shm[k], shs[k]);
   const float lse = m + __logf(s);
   const bool valid = t >= 0 && t < V;
-  if (tid == 0) loss_rows[row] = valid ? lse - xt : 0.f;
+  if constexpr (SMOOTH) {
+    if (tid == 0)
+      loss_rows[row] = xent_smooth_loss(sm, wr, lse, xt, (shq[0] + shq[1]) + (shq[2] + shq[3]));
+  } else {
+    if (tid == 0) loss_rows[row] = valid ? lse - xt : 0.f;
+  }
   if (!write_grad) return;
   const float sc = valid ? scale : 0.f;
+  const float kf = SMOOTH ? fmaf(2.f * sm.z, lse, 1.f) : 1.f;   // 1 + 2 z lse
   for (c = tid; c < nch; c += 256) {
     float v[8];
     unpack8(Lr[c], v);
@@ -578,18 +694,23 @@ __global__ __launch_bounds__(256) void k_xent_bf16(bf16_t* __restrict__ L, const
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int col = col0 + e;
-      const float p = col < V ? __expf(v[e] - lse) : 0.f;
-      v[e] = (p - (col == t ? 1.f : 0.f)) * sc;
+      if constexpr (SMOOTH) {
+        const float g = ((kf * __expf(v[e] - lse) - (col == t ? sm.keep : 0.f)) - sm.spread) * sc;
+        v[e] = col < V ? g : 0.f;
+      } else {
+        const float p = col < V ? __expf(v[e] - lse) : 0.f;
+        v[e] = (p - (col == t ? 1.f : 0.f)) * sc;
+      }
     }
     Lr[c] = pack8(v);
   }
 }
 
 // the launcher's names of the two register-resident kernels at GPT-2's row width
-template <bool MASK>
-constexpr auto k_xent_bf16_reg25 = k_xent_bf16_reg<25, MASK>;
-template <bool MASK>
-constexpr auto k_xent_bf16_reg2_25 = k_xent_bf16_reg2<25, MASK>;
+template <bool MASK, bool SMOOTH>
+constexpr auto k_xent_bf16_reg25 = k_xent_bf16_reg<25, MASK, SMOOTH>;
+template <bool MASK, bool SMOOTH>
+constexpr auto k_xent_bf16_reg2_25 = k_xent_bf16_reg2<25, MASK, SMOOTH>;
 
 // ---------------------------------------------------------------------------------- embeddings
 // DROP: embedding dropout applied while writing (element index = offset in the [N, C] output)
@@ -1126,18 +1247,24 @@ hipError_t pde_gelu_bwd(const void* dY, const void* X, void* dX, int64_t n, hipS
   return hipGetLastError();
 }
 
-// scale_dev (nullable): the MASK instantiations (scale * scale_dev[0], ignored rows leave early)
-hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
-                         int write_grad, const float* scale_dev, hipStream_t st) {
+// scale_dev (nullable): the MASK instantiations (scale * scale_dev[0], ignored rows leave early); smooth: the
+// SMOOTH ones, which need scale_dev.  The routes are the same for all three.
+static hipError_t xent_bf16_launch(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale,
+                                   float* loss_rows, int write_grad, const float* scale_dev, bool smooth,
+                                   PdeXentSmooth sm, hipStream_t st) {
+  if (smooth && !scale_dev) return hipErrorInvalidValue;
   if (N == 0) return hipSuccess;
-#define XENT(K)                                                                                              \
-  do {                                                                                                       \
-    if (scale_dev)                                                                                           \
-      hipLaunchKernelGGL((K<true>), dim3(N), dim3(256), 0, st, (bf16_t*)logits, tgt, Vp, V, scale, loss_rows,   \
-                         write_grad, scale_dev);                                                             \
-    else                                                                                                     \
-      hipLaunchKernelGGL((K<false>), dim3(N), dim3(256), 0, st, (bf16_t*)logits, tgt, Vp, V, scale, loss_rows,  \
-                         write_grad, scale_dev);                                                             \
+#define XENT_AS(K, MASK, SMOOTH)                                                                                \
+  hipLaunchKernelGGL((K<MASK, SMOOTH>), dim3(N), dim3(256), 0, st, (bf16_t*)logits, tgt, Vp, V, scale, loss_rows, \
+                     write_grad, scale_dev, sm)
+#define XENT(K)                                 \
+  do {                                          \
+    if (smooth)                                 \
+      XENT_AS(K, false, true);                  \
+    else if (scale_dev)                         \
+      XENT_AS(K, true, false);                  \
+    else                                        \
+      XENT_AS(K, false, false);                 \
   } while (0)
   if ((Vp >> 3) <= 256 * 25 && Vp >= 256 * 8 * 16) {   // wide rows (GPT-2 vocab): one read, one write
     const char* env = getenv("PDE_XENT_V");            // 1: the two-exp online-softmax kernel (A/B)
@@ -1154,7 +1281,19 @@ hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V,
   }
   XENT(k_xent_bf16);
 #undef XENT
+#undef XENT_AS
   return hipGetLastError();
+}
+
+hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
+                         int write_grad, const float* scale_dev, hipStream_t st) {
+  return xent_bf16_launch(logits, tgt, N, Vp, V, scale, loss_rows, write_grad, scale_dev, false,
+                          PdeXentSmooth{nullptr, 1.f, 0.f, 0.f}, st);
+}
+
+hipError_t pde_xent_bf16_smooth(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
+                                int write_grad, const float* scale_dev, PdeXentSmooth sm, hipStream_t st) {
+  return xent_bf16_launch(logits, tgt, N, Vp, V, scale, loss_rows, write_grad, scale_dev, true, sm, st);
 }
 
 hipError_t pde_loss_targets(PdeLossTargets a, hipStream_t st) {

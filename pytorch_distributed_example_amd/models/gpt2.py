@@ -212,7 +212,7 @@ class GPT(tnn.Module):
         return self.training and (c.embd_pdrop > 0.0 or c.attn_pdrop > 0.0 or c.resid_pdrop > 0.0)
 
     def forward(self, idx, targets=None, doc_ids=None, *, ignore_index=None, loss_mask=None, mask_doc_ends=False,
-                reduction="mean", denom=None):
+                reduction="mean", denom=None, label_smoothing=0.0, z_loss=0.0, loss_weights=None):
         """Logits ``[B, T, V]``, or the mean cross-entropy against ``targets``.
 
         ``doc_ids`` (an integer ``[B, T]`` tensor on the model's device) marks packed rows: a document
@@ -231,7 +231,13 @@ class GPT(tnn.Module):
         ``denom`` (an fp32 device scalar) replaces the count as the denominator, for a global mean over
         data-parallel ranks or accumulated micro-batches; ``reduction`` is ``"mean"``, ``"sum"`` or
         ``"none"`` (per-position losses, no gradient).  The valid count stays on the device, so a captured
-        step follows every batch."""
+        step follows every batch.
+
+        ``label_smoothing`` (in ``[0, 1)``), ``z_loss`` (``>= 0``, the coefficient of ``lse^2``) and
+        ``loss_weights`` (a floating ``[B, T]`` tensor, one weight per target) select the smoothed and weighted
+        loss defined in ``ops.transformer.lm_head_loss``.  The mean still divides by the number of valid
+        targets, whatever their weights (pass the weights' sum as ``denom`` for a weighted mean).  The two
+        numbers are frozen into a captured step; the weights are device data and follow every replay."""
         if mask_doc_ends and doc_ids is None:
             raise ValueError("GPT.forward: mask_doc_ends=True needs doc_ids")
         t = self.transformer
@@ -260,7 +266,8 @@ class GPT(tnn.Module):
             return T.lm_logits(x, t.wte.weight, self.config.vocab_size)
         return T.lm_head_loss(x, t.wte.weight, targets, self.config.vocab_size, ignore_index=ignore_index,
                               loss_mask=loss_mask, doc_bounds=bounds if mask_doc_ends else None,
-                              mask_doc_ends=mask_doc_ends, reduction=reduction, denom=denom)
+                              mask_doc_ends=mask_doc_ends, reduction=reduction, denom=denom,
+                              label_smoothing=label_smoothing, z_loss=z_loss, loss_weights=loss_weights)
 
     # ------------------------------------------------------------------------------- generation
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, seed=None, generator=None,

@@ -585,13 +585,14 @@ class LMHeadLossFn(torch.autograd.Function):
 
     Forward runs the GEMM and the fused softmax-CE kernel, which overwrites the logits buffer with
     dlogits = (softmax - onehot) / N (masked loss: times ``inv[0]``, a device value, and exact zeros in
-    rows that do not count); backward is two GEMMs from that buffer with the incoming loss
+    rows that do not count; ``smooth = (label_smoothing, z_loss, weights or None)``: the smoothed and weighted
+    gradient of ``lm_head_loss``, still written by the same kernel); backward is two GEMMs from that buffer with the incoming loss
     gradient applied in their epilogues (a device scalar: no host read, no extra kernel, graph-safe,
     and the saved dlogits stay unscaled, so a retained graph can run backward again).  With W tied to
     the embedding of the same forward pass, dW is left for the embedding backward to accumulate into."""
 
     @staticmethod
-    def forward(ctx, h, w, targets, V, inv=None):
+    def forward(ctx, h, w, targets, V, inv=None, smooth=None):
         C = h.shape[-1]
         h2 = _c(h.reshape(-1, C))
         N = h2.shape[0]
@@ -604,8 +605,12 @@ class LMHeadLossFn(torch.autograd.Function):
         if inv is None:
             kernels().xent_bf16(logits, tg, V, 1.0 / N, rows, True)
             kernels().sum_f32(rows, tot, 1.0 / N)               # mean loss, no separate divide
-        else:   # masked loss: targets are loss_targets' effective ones, inv its device-side 1 / denominator
+        elif smooth is None:   # masked loss: targets are loss_targets' effective ones, inv its device-side 1 / denominator
             kernels().xent_bf16(logits, tg, V, 1.0, rows, True, scale_dev=inv)
+            kernels().sum_f32(rows, tot, 1.0, scale_dev=inv)
+        else:   # the rows come out weighted, so the sum is the masked loss's
+            kernels().xent_bf16(logits, tg, V, 1.0, rows, True, scale_dev=inv, label_smoothing=smooth[0],
+                                z_loss=smooth[1], loss_weights=smooth[2])
             kernels().sum_f32(rows, tot, 1.0, scale_dev=inv)
         ctx.save_for_backward(h2, w, logits)
         ctx.hshape = h.shape
@@ -626,11 +631,34 @@ class LMHeadLossFn(torch.autograd.Function):
         dw, _ = G.wgrad(dlogits, h2, dw=_grad_out(w), scale=gs)   # [Vp, C]
         if ctx.tied is not None:
             ctx.tied["dw"] = dw                              # the tied embedding adds its part in place
-        return dh.reshape(ctx.hshape), dw, None, None, None
+        return dh.reshape(ctx.hshape), dw, None, None, None, None
+
+
+def _check_smoothing(label_smoothing, z_loss, loss_weights, targets):
+    """``(eps, zc, weights)`` of ``lm_head_loss``, validated: two host floats and the weights as a contiguous fp32
+    vector (or None)."""
+    try:
+        eps, zc = float(label_smoothing), float(z_loss)
+    except (TypeError, ValueError):
+        raise ValueError(f"lm_head_loss: label_smoothing and z_loss must be numbers, got {label_smoothing!r} and "
+                         f"{z_loss!r}") from None
+    if not (math.isfinite(eps) and 0.0 <= eps < 1.0):
+        raise ValueError(f"lm_head_loss: label_smoothing must be in [0, 1), got {label_smoothing!r}")
+    if not (math.isfinite(zc) and zc >= 0.0):
+        raise ValueError(f"lm_head_loss: z_loss must be finite and >= 0, got {z_loss!r}")
+    if loss_weights is None:
+        return eps, zc, None
+    if not (torch.is_tensor(loss_weights) and loss_weights.is_floating_point()):
+        raise ValueError(f"lm_head_loss: loss_weights must be a floating tensor, got "
+                         f"{getattr(loss_weights, 'dtype', type(loss_weights))} (a 0/1 selection is loss_mask)")
+    if tuple(loss_weights.shape) != tuple(targets.shape) or loss_weights.device != targets.device:
+        raise ValueError(f"lm_head_loss: loss_weights must have the targets' shape and device (got "
+                         f"{tuple(loss_weights.shape)} on {loss_weights.device})")
+    return eps, zc, _c(loss_weights.detach().reshape(-1).float())
 
 
 def lm_head_loss(h, w, targets, V: int, *, ignore_index=None, loss_mask=None, doc_bounds=None, mask_doc_ends=False,
-                 reduction="mean", denom=None):
+                 reduction="mean", denom=None, label_smoothing=0.0, z_loss=0.0, loss_weights=None):
     """Cross-entropy of ``logits = h @ w[:V]^T`` against ``targets``.
 
     With every keyword at its default this is the call as it was: the mean over all ``N`` targets (on the
@@ -644,9 +672,33 @@ def lm_head_loss(h, w, targets, V: int, *, ignore_index=None, loss_mask=None, do
     reaches the host, so a captured step follows the batch.
 
     ``reduction``: ``"mean"``, ``"sum"`` (no ``denom``), or ``"none"``: the per-position losses, fp32 in the
-    input's leading shape, 0 where not valid; no gradient (``NotImplementedError`` if one is asked for)."""
+    input's leading shape, 0 where not valid; no gradient (``NotImplementedError`` if one is asked for).
+
+    ``label_smoothing`` (``eps`` in ``[0, 1)``), ``z_loss`` (``zc >= 0``) and ``loss_weights`` (a floating tensor
+    of the targets' shape on their device, used as fp32; ``w_i = 1`` when None) select the smoothed and weighted
+    loss.  For row ``i`` with logits ``x``, ``lse = logsumexp(x[:V])``, ``p = softmax(x[:V])`` and effective
+    target ``t``, with ``valid(i)`` and ``inv`` exactly those of ``loss_targets``::
+
+        row_i         = w_i * (lse - (1 - eps) * x[t] - (eps / V) * sum_{v<V} x[v] + zc * lse^2)   valid(i), else 0
+        loss          = inv * sum_i row_i
+        dlogits[i, v] = w_i * inv * ((1 + 2 * zc * lse) * p[v] - (1 - eps) * [v == t] - eps / V)   v < V, valid(i)
+                      = exact 0                                                                    v >= V, or not valid(i)
+
+    * ``zc = 0`` and no weights: ``F.cross_entropy(..., label_smoothing=eps)``, its ``ignore_index`` mean
+      included (torch also divides by the number of targets that are not ignored).
+    * ``count`` and ``inv`` do not change with the weights: the mean divides by the number of valid rows, and a
+      weight of 0 is a valid row that contributes zeros.  For a weighted mean pass the weights' sum over the
+      valid rows as ``denom``: ``lt = ops.loss_targets(...)``, then
+      ``denom = (loss_weights * (lt.targets >= 0)).sum()`` -- device ops, no host read.
+    * The weight of a row that is not valid is never read: NaN there is as harmless as NaN logits there.
+    * ``eps`` and ``zc`` are host floats, frozen into a captured launch as dropout's ``p`` is; ``loss_weights``
+      is device data and follows every replay.
+    * Any value away from these defaults runs ``loss_targets`` and the ``SMOOTH`` kernels, also without a mask:
+      every in-range row is then valid and ``inv = 1 / N``.  ``reduction="none"`` returns ``row_i``."""
+    eps, zc, wts = _check_smoothing(label_smoothing, z_loss, loss_weights, targets)
+    smooth = eps != 0.0 or zc != 0.0 or wts is not None
     if (ignore_index is None and loss_mask is None and doc_bounds is None and not mask_doc_ends
-            and reduction == "mean" and denom is None):
+            and reduction == "mean" and denom is None and not smooth):
         if _gpu(h):
             return LMHeadLossFn.apply(h, w, targets, V)
         logits = torch.matmul(h, w.t())[..., :V].float()
@@ -657,16 +709,37 @@ def lm_head_loss(h, w, targets, V: int, *, ignore_index=None, loss_mask=None, do
         raise NotImplementedError("lm_head_loss: reduction='none' has no backward; call it under torch.no_grad()")
     if _gpu(h):
         if reduction != "none":
+            if smooth:
+                return LMHeadLossFn.apply(h, w, lt.targets, V, lt.inv, (eps, zc, wts))
             return LMHeadLossFn.apply(h, w, lt.targets, V, lt.inv)
         C = h.shape[-1]
         h2 = _c(h.reshape(-1, C))
         rows = torch.empty(h2.shape[0], device=h.device, dtype=torch.float32)
         # loss only (write_grad = 0): the logits stay as they are, ignored rows are not read
-        kernels().xent_bf16(G.fprop(h2, w, nt_out=True), _c(lt.targets.reshape(-1)), V, 1.0, rows, False,
-                            scale_dev=lt.inv)
+        if smooth:
+            kernels().xent_bf16(G.fprop(h2, w, nt_out=True), _c(lt.targets.reshape(-1)), V, 1.0, rows, False,
+                                scale_dev=lt.inv, label_smoothing=eps, z_loss=zc, loss_weights=wts)
+        else:
+            kernels().xent_bf16(G.fprop(h2, w, nt_out=True), _c(lt.targets.reshape(-1)), V, 1.0, rows, False,
+                                scale_dev=lt.inv)
         return rows.view(h.shape[:-1])
     eff = lt.targets.reshape(-1)
     valid = eff >= 0
+    if smooth:
+        x = torch.matmul(h, w.t())[..., :V].reshape(-1, V)
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.float()
+        # as below: an invalid row (and its weight) is taken out before anything is computed from it
+        x = torch.where(valid[:, None], x, x.new_zeros(()))
+        lse = torch.logsumexp(x, 1)
+        xt = x.gather(1, eff.clamp(min=0)[:, None])[:, 0]
+        rows = lse - (1.0 - eps) * xt - (eps / V) * x.sum(1) + zc * lse * lse
+        if wts is not None:
+            rows = rows * torch.where(valid, wts, wts.new_zeros(())).to(x.dtype)
+        rows = torch.where(valid, rows, rows.new_zeros(()))
+        if reduction == "none":
+            return rows.view(h.shape[:-1])
+        return rows.sum() * lt.inv
     logits = torch.matmul(h, w.t())[..., :V].float().reshape(-1, V)
     # an ignored row counts as zeros whatever it holds: taken out before the softmax, so NaN cannot leak
     logits = torch.where(valid[:, None], logits, logits.new_zeros(()))
