@@ -100,9 +100,10 @@ void decode_embed(const at::Tensor& tok, const at::Tensor& wte, const at::Tensor
             "decode_embed");
 }
 
-void sample(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next, const at::Tensor& out,
-            const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k, int64_t eos,
-            const OptT& thr_out, double top_p) {
+// the checked arguments shared by both sampler entries
+PdeSample sample_args(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next,
+                      const at::Tensor& out, const OptT& logits_out, int64_t T0, double inv_temp, bool greedy,
+                      int64_t top_k, int64_t eos, const OptT& thr_out, double top_p) {
   check_cuda(logits, "logits", BF16);
   TORCH_CHECK(logits.dim() == 2 && logits.size(1) % 8 == 0, "sample: logits must be [B, Vp] with Vp % 8 == 0");
   const int64_t B = logits.size(0), Vp = logits.size(1);
@@ -140,7 +141,70 @@ void sample(const at::Tensor& logits, int64_t V, const at::Tensor& state, const 
   a.top_k = (int)top_k;
   a.eos = (int)eos;
   a.top_p = top_p;
-  hip_check(pde_sample(a, cur_stream()), "sample");
+  return a;
+}
+
+void sample(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next, const at::Tensor& out,
+            const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k, int64_t eos,
+            const OptT& thr_out, double top_p) {
+  hip_check(pde_sample(sample_args(logits, V, state, next, out, logits_out, T0, inv_temp, greedy, top_k, eos, thr_out,
+                                   top_p),
+                       cur_stream()),
+            "sample");
+}
+
+// The sampler with the logit processors (PdeSampleProc in pde_decode.h).  counts: int32 [B, Vp]; bias: fp32
+// [1 or B, Vp] or None; work: bf16 [B, Vp], receives the processed logits; rep / inv_rep: fp32(r), fp32(1 / r).
+void sample_proc(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next,
+                 const at::Tensor& out, const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k,
+                 int64_t eos, const OptT& thr_out, double top_p, const at::Tensor& counts, const OptT& bias,
+                 const at::Tensor& work, double rep, double inv_rep, double freq, double pres, int64_t min_new) {
+  const PdeSample a = sample_args(logits, V, state, next, out, logits_out, T0, inv_temp, greedy, top_k, eos, thr_out,
+                                  top_p);
+  const int64_t B = a.B, Vp = a.Vp;
+  check_cuda(counts, "counts", I32, B * Vp);
+  TORCH_CHECK(counts.dim() == 2 && counts.size(0) == B && counts.size(1) == Vp, "sample: counts must be [B, Vp]");
+  check_al16(counts, "counts");
+  check_cuda(work, "processed_out", BF16, B * Vp);
+  TORCH_CHECK(work.dim() == 2 && work.size(0) == B && work.size(1) == Vp, "sample: processed_out must be [B, Vp]");
+  check_al16(work, "processed_out");
+  TORCH_CHECK(work.data_ptr() != logits.data_ptr(), "sample: processed_out must not be the logits");
+  PdeSampleProc p{};
+  p.counts = ptr<int>(counts);
+  p.work = work.data_ptr();
+  p.bias = nullptr;
+  p.bias_stride = 0;
+  if (bias.has_value() && bias->defined()) {
+    check_cuda(*bias, "bias", F32);
+    TORCH_CHECK(bias->dim() == 2 && (bias->size(0) == 1 || bias->size(0) == B) && bias->size(1) == Vp,
+                "sample: the padded bias must be [1 or B, Vp]");
+    check_al16(*bias, "bias");
+    p.bias = ptr<float>(*bias);
+    p.bias_stride = bias->size(0) == 1 ? 0 : (int)Vp;
+  }
+  TORCH_CHECK(rep > 0.0 && inv_rep > 0.0, "sample: repetition penalty must be > 0");
+  TORCH_CHECK(min_new >= 0 && (min_new == 0 || eos >= 0), "sample: min_new_tokens >= 0, and > 0 needs eos");
+  p.min_new = (int)std::min<int64_t>(min_new, INT32_MAX);
+  p.rep = (float)rep;
+  p.inv_rep = (float)inv_rep;
+  p.freq = (float)freq;
+  p.pres = (float)pres;
+  hip_check(pde_sample_proc(a, p, cur_stream()), "sample");
+}
+
+// counts[b, idx[b, t]] = prompt flag for t < T0 + the state's offset of row b; idx: int64 [B, width]
+void count_prompt(const at::Tensor& idx, const at::Tensor& state, const at::Tensor& counts, int64_t T0) {
+  check_cuda(idx, "idx", I64);
+  TORCH_CHECK(idx.dim() == 2 && idx.size(1) >= 1, "count_prompt: idx must be [B, width >= 1]");
+  const int64_t B = idx.size(0), Vp = counts.dim() == 2 ? counts.size(1) : 0;
+  TORCH_CHECK(B >= 1 && B <= PDE_DS_MAX_ROWS, "count_prompt: 1 <= B <= ", PDE_DS_MAX_ROWS, ", got ", B);
+  check_cuda(counts, "counts", I32, B * Vp);
+  TORCH_CHECK(counts.dim() == 2 && counts.size(0) == B && Vp >= 1, "count_prompt: counts must be [B, Vp]");
+  TORCH_CHECK(T0 >= 0 && T0 <= idx.size(1), "count_prompt: 0 <= T0 <= width");
+  check_state(state);
+  hip_check(pde_count_prompt(ptr<int64_t>(idx), ptr<int>(state), ptr<int>(counts), (int)B, (int)idx.size(1),
+                             (int)idx.size(1), (int)T0, (int)Vp, cur_stream()),
+            "count_prompt");
 }
 
 }  // namespace
@@ -157,6 +221,11 @@ void register_decode(pybind11::module& m) {
   m.def("decode_sample", &sample, py::arg("logits"), py::arg("V"), py::arg("state"), py::arg("next"), py::arg("out"),
         py::arg("logits_out"), py::arg("T0"), py::arg("inv_temp"), py::arg("greedy"), py::arg("top_k"), py::arg("eos"),
         py::arg("thr_out") = py::none(), py::arg("top_p") = 0.0);
+  m.def("decode_sample_proc", &sample_proc, py::arg("logits"), py::arg("V"), py::arg("state"), py::arg("next"),
+        py::arg("out"), py::arg("logits_out"), py::arg("T0"), py::arg("inv_temp"), py::arg("greedy"), py::arg("top_k"),
+        py::arg("eos"), py::arg("thr_out"), py::arg("top_p"), py::arg("counts"), py::arg("bias"), py::arg("work"),
+        py::arg("rep"), py::arg("inv_rep"), py::arg("freq"), py::arg("pres"), py::arg("min_new"));
+  m.def("decode_count_prompt", &count_prompt);
   m.attr("DECODE_STATE_WORDS") = PDE_DS_WORDS;
 }
 

@@ -14,6 +14,14 @@
 //                T0 + off_b + step, with T0 = max(len) the launch argument.  All zero: one prompt length.
 //
 // The sampler launch reads the state; its one-thread tail kernel advances p, step and the draw number.
+//
+// The logit processors (repetition / frequency / presence penalties, logit bias, min_new_tokens) keep their
+// history in a buffer of their own, the token counts: int32 [B, Vp], word (b, v) =
+//
+//   bit  30      token v occurs in the prompt of row b (set once by pde_count_prompt, never cleared)
+//   bits 0..29   n_v: how often row b has generated v so far (the sampler adds 1 at the token it emits)
+//
+// so "seen" is word != 0.  The state and its 40 words do not change.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -25,6 +33,8 @@
 #define PDE_DS_MAX_ROWS 16
 #define PDE_DS_OFF 24
 #define PDE_DS_WORDS 40
+#define PDE_TC_PROMPT 0x40000000       // token counts: the prompt flag
+#define PDE_TC_COUNT 0x3fffffff        // token counts: mask of n_v
 
 #ifdef __cplusplus
 extern "C" {
@@ -66,6 +76,31 @@ typedef struct PdeSample {
   double top_p;         // nucleus mass in (0, 1); 0 or >= 1: off.  Unused when greedy
 } PdeSample;
 hipError_t pde_sample(PdeSample a, hipStream_t st);
+
+// The logit processors of a sampler launch.  With x the fp32 value of a logit, c the counts word of (b, v),
+// n = c & PDE_TC_COUNT and s the state's step, every operation rounded on its own (no fused multiply-add):
+//   if (c != 0) x = x > 0 ? x * inv_rep : x * rep;
+//   x = (x - freq * float(n)) - (n > 0 ? pres : 0);
+//   if (bias) x = x + bias[b * bias_stride + v];
+//   if (s < min_new && v == eos) x = -inf;
+//   y = bf16(x), round-to-nearest-even
+// The sampler of pde_sample then runs on y, and counts[b, token] += 1.  logits_out keeps receiving the raw row.
+typedef struct PdeSampleProc {
+  int* counts;          // [B, Vp] token counts
+  const float* bias;    // [1 or B, Vp] fp32 (pad columns 0), 16-byte aligned, or null
+  void* work;           // [B, Vp] bf16, 16-byte aligned: receives y (all Vp columns of every row)
+  int bias_stride;      // Vp, or 0 for one row shared by the batch
+  int min_new;          // 0: off; needs eos >= 0 otherwise
+  float rep, inv_rep;   // fp32(r), fp32(1 / r); 1, 1: off
+  float freq, pres;
+} PdeSampleProc;
+hipError_t pde_sample_proc(PdeSample a, PdeSampleProc p, hipStream_t st);
+
+// counts[b, idx[b, t]] = PDE_TC_PROMPT for t < len_b = T0 + state[PDE_DS_OFF + b] (clamped to [0, width]); idx is
+// [B, width] with row stride `stride`.  To be called on zeroed counts: duplicates store the same word, so the
+// stores need no atomic.  Tokens outside [0, Vp) are skipped.
+hipError_t pde_count_prompt(const int64_t* idx, const int* state, int* counts, int B, int width, int stride, int T0,
+                            int Vp, hipStream_t st);
 
 #ifdef __cplusplus
 }

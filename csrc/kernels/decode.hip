@@ -25,6 +25,10 @@
 //                   weighted by exp(z - z_max) in 64-bit fixed point: integer LDS atomics sum in any order
 //                   to the same bits, which float atomics would not.  It is a template instantiation of
 //                   its own, so the sampler without top-p is the code it was.
+//   processors      penalties, logit bias and min_new_tokens live in the sampler, the only place where a decode
+//                   step's logits and the rows' histories meet: two more instantiations (PROC) write the
+//                   processed row to a bf16 workspace first and then run the same passes on it; the history is a
+//                   [B, Vp] counts buffer that the kernel reads and advances, so a captured step follows it.
 //   ragged batches  row b sits at position p_b = state position + state offset of row b; every block of
 //                   the attention, the embedding and the sampler derives what it does from its own p_b.
 #include "pde_hip.h"
@@ -275,294 +279,8 @@ __global__ __launch_bounds__(256) void k_dec_embed(const int64_t* __restrict__ t
 }
 
 // ------------------------------------------------------------------------------------- sampler
-// order-preserving 16-bit key of a bf16 value (-0 counts as +0, as in a float compare)
-__device__ __forceinline__ uint32_t key16(uint32_t u) {
-  u &= 0xffffu;
-  if (u == 0x8000u) u = 0u;
-  return (u & 0x8000u) ? (~u & 0xffffu) : (u | 0x8000u);
-}
-__device__ __forceinline__ uint32_t fkey32(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
-    const uint64_t t = ((uint64_t)hi << 32) | lo;
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
-// wave 0: the bin (counting from bin 255 down) that holds the k-th largest element, and k's rank inside it.
-// hist: [4 waves][256 bins]; sel[0] = bin, sel[1] = rank left
-__device__ __forceinline__ void radix_pick(const uint32_t (*hist)[256], uint32_t k, uint32_t* sel) {
-  const int l = threadIdx.x;    // 0..63
-  uint32_t cnt[4], c = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    cnt[q] = hist[0][4 * l + q] + hist[1][4 * l + q] + hist[2][4 * l + q] + hist[3][4 * l + q];
-    c += cnt[q];
-  }
-  uint32_t s = c;               // suffix sum over lanes >= l
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_down(s, o, 64);
-    if (l + o < 64) s += t;
-  }
-  const uint32_t excl = s - c;
-  if (excl < k && k <= s) {
-    uint32_t rem = k - excl;
-    int bin = 4 * l;
-#pragma unroll
-    for (int q = 3; q >= 0; --q) {
-      if (rem <= cnt[q]) {
-        bin = 4 * l + q;
-        break;
-      }
-      rem -= cnt[q];
-    }
-    sel[0] = (uint32_t)bin;
-    sel[1] = rem;
-  }
-}
-
-// wave 0, weighted form: the bin (counting from bin 255 down) at which the running mass first reaches
-// `target`, and the part of the target that bin has to cover.  whist: [4 waves][256 bins] of fixed-point mass;
-// 1 <= target <= total mass, so exactly one lane writes.  wsel[0] = bin, wsel[1] = target left
-__device__ __forceinline__ void radix_pick_mass(const uint64_t (*whist)[256], uint64_t target, uint64_t* wsel) {
-  const int l = threadIdx.x;    // 0..63
-  uint64_t cnt[4], c = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    cnt[q] = whist[0][4 * l + q] + whist[1][4 * l + q] + whist[2][4 * l + q] + whist[3][4 * l + q];
-    c += cnt[q];
-  }
-  uint64_t s = c;               // suffix sum over lanes >= l
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t lo = __shfl_down((uint32_t)s, o, 64), hi = __shfl_down((uint32_t)(s >> 32), o, 64);
-    if (l + o < 64) s += ((uint64_t)hi << 32) | lo;
-  }
-  const uint64_t excl = s - c;
-  if (excl < target && target <= s) {
-    uint64_t rem = target - excl;
-    int bin = 4 * l;
-#pragma unroll
-    for (int q = 3; q >= 0; --q) {
-      if (rem <= cnt[q]) {
-        bin = 4 * l + q;
-        break;
-      }
-      rem -= cnt[q];
-    }
-    wsel[0] = (uint64_t)bin;
-    wsel[1] = rem;
-  }
-}
-
-// 2^40 * exp(z - zmax), rounded: the mass of one candidate in fixed point (z <= zmax, so at most 2^40)
-__device__ __forceinline__ uint64_t mass_fx(float z, float zmax) {
-  return (uint64_t)rintf(expf(z - zmax) * 1099511627776.0f);
-}
-
-// The nucleus stage: among the candidates (key16 >= thr) the key of the largest logit value t with
-// mass{logit >= t} >= top_p * total mass.  Same two 8-bit passes as the top-k select, with every candidate
-// counted by its mass; the sums are integers, so the result does not depend on the order of the atomics.
-// All threads of the block call it; whist / wsel / wmax are its LDS.
-__device__ __forceinline__ uint32_t nucleus_threshold(const bf16_t* __restrict__ row, int V, int ngrp, uint32_t thr,
-                                                      float inv_temp, double top_p, uint64_t (*whist)[256],
-                                                      uint64_t* wsel, uint32_t* wmax, int nthreads) {
-  const int tid = threadIdx.x, w = tid >> 6;
-  if (tid == 0) wsel[0] = wsel[1] = 0ull;     // a row of NaNs has no mass and picks nothing: key 0 then
-  // the largest key of the row: always a candidate, and z is monotone in the key (inv_temp > 0)
-  uint32_t mk = 0;
-  for (int gi = tid; gi < ngrp; gi += nthreads) {
-    const uint2 w2 = reinterpret_cast<const uint2*>(row)[gi];
-    const uint32_t u[4] = {w2.x & 0xffffu, w2.x >> 16, w2.y & 0xffffu, w2.y >> 16};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const uint32_t key = 4 * gi + e < V ? key16(u[e]) : 0u;
-      mk = key > mk ? key : mk;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t t = __shfl_xor(mk, o, 64);
-    mk = t > mk ? t : mk;
-  }
-  if ((tid & 63) == 0) wmax[w] = mk;
-  __syncthreads();
-  for (int i = 0; i < nthreads / 64; ++i) mk = wmax[i] > mk ? wmax[i] : mk;
-  const uint32_t mbits = (mk & 0x8000u) ? (mk & 0x7fffu) : (~mk & 0xffffu);     // key16 inverted
-  const float zmax = bf2f(mbits) * inv_temp;
-
-  uint32_t hi = 0;
-  uint64_t target = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int i = tid; i < 1024; i += nthreads) (&whist[0][0])[i] = 0ull;
-    __syncthreads();
-    for (int gi = tid; gi < ngrp; gi += nthreads) {
-      const uint2 w2 = reinterpret_cast<const uint2*>(row)[gi];
-      const uint32_t u[4] = {w2.x & 0xffffu, w2.x >> 16, w2.y & 0xffffu, w2.y >> 16};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (4 * gi + e >= V) continue;
-        const uint32_t key = key16(u[e]);
-        if (key < thr) continue;
-        if (pass == 0) atomicAdd((unsigned long long*)&whist[w & 3][key >> 8],
-                                 (unsigned long long)mass_fx(bf2f(u[e]) * inv_temp, zmax));
-        else if ((key >> 8) == hi) atomicAdd((unsigned long long*)&whist[w & 3][key & 0xffu],
-                                             (unsigned long long)mass_fx(bf2f(u[e]) * inv_temp, zmax));
-      }
-    }
-    __syncthreads();
-    if (pass == 0) {
-      if (tid < 64) {          // total mass -> target, by every lane of wave 0 alike
-        uint64_t c = 0;
-        for (int q = 0; q < 4; ++q)
-          c += whist[0][4 * tid + q] + whist[1][4 * tid + q] + whist[2][4 * tid + q] + whist[3][4 * tid + q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const uint32_t lo = __shfl_xor((uint32_t)c, o, 64), h2 = __shfl_xor((uint32_t)(c >> 32), o, 64);
-          c += ((uint64_t)h2 << 32) | lo;
-        }
-        uint64_t t = (uint64_t)ceil(top_p * (double)c);
-        t = t < 1 ? 1 : (t > c ? c : t);
-        radix_pick_mass(whist, t, wsel);
-      }
-    } else if (w == 0) {
-      radix_pick_mass(whist, target, wsel);
-    }
-    __syncthreads();
-    if (pass == 0) {
-      hi = (uint32_t)wsel[0];
-      target = wsel[1];
-    }
-    __syncthreads();
-  }
-  return (hi << 8) | (uint32_t)wsel[0];
-}
-
-// grid B, block SM_NT (16 waves: a row of 50304 logits is ~50 per thread and pass; the 4 histograms are
-// shared by waves w, w + 4, ...).  TOPP adds the nucleus stage between the top-k select and the Gumbel pass.
-constexpr int SM_NT = 1024;
-template <bool TOPP>
-__global__ __launch_bounds__(SM_NT) void k_sample(PdeSample a) {
-  __shared__ uint32_t hist[4][256];
-  __shared__ uint32_t sel[2];
-  __shared__ uint64_t bred[SM_NT / 64];
-  const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
-  const bf16_t* row = reinterpret_cast<const bf16_t*>(a.logits) + (size_t)b * a.Vp;
-  const uint32_t st[4] = {(uint32_t)a.state[PDE_DS_RNG], (uint32_t)a.state[PDE_DS_RNG + 1],
-                          (uint32_t)a.state[PDE_DS_RNG + 2], (uint32_t)a.state[PDE_DS_RNG + 3]};
-  const int step = a.state[PDE_DS_STEP];
-  const int fin = a.state[PDE_DS_FIN + b];
-  const int slot = a.T0 + a.state[PDE_DS_OFF + b] + step;      // read here, with the other state words
-  const int V = a.V, ngrp = a.Vp >> 2;
-
-  uint32_t thr = 0;             // candidates: key16 >= thr
-  if (!a.greedy && a.top_k > 0 && a.top_k < V) {
-    uint32_t hi = 0, k = (uint32_t)a.top_k;
-    for (int pass = 0; pass < 2; ++pass) {
-      for (int i = tid; i < 1024; i += SM_NT) (&hist[0][0])[i] = 0u;
-      __syncthreads();
-      for (int gi = tid; gi < ngrp; gi += SM_NT) {
-        const uint2 w2 = reinterpret_cast<const uint2*>(row)[gi];
-        const uint32_t u[4] = {w2.x & 0xffffu, w2.x >> 16, w2.y & 0xffffu, w2.y >> 16};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (4 * gi + e >= V) continue;
-          const uint32_t key = key16(u[e]);
-          if (pass == 0) atomicAdd(&hist[w & 3][key >> 8], 1u);
-          else if ((key >> 8) == hi) atomicAdd(&hist[w & 3][key & 0xffu], 1u);
-        }
-      }
-      __syncthreads();
-      if (w == 0) radix_pick(hist, k, sel);
-      __syncthreads();
-      if (pass == 0) {
-        hi = sel[0];
-        k = sel[1];
-      } else {
-        thr = (hi << 8) | sel[0];
-      }
-      __syncthreads();
-    }
-  }
-  if constexpr (TOPP) {
-    if (!a.greedy) {
-      __shared__ uint64_t whist[4][256];
-      __shared__ uint64_t wsel[2];
-      __shared__ uint32_t wmax[SM_NT / 64];
-      thr = nucleus_threshold(row, V, ngrp, thr, a.inv_temp, a.top_p, whist, wsel, wmax, SM_NT);
-    }
-  }
-
-  // best = max over candidates of (score key << 32 | ~index): highest score, lowest index on ties
-  uint64_t best = 0;
-  for (int gi = tid; gi < ngrp; gi += SM_NT) {
-    const uint2 w2 = reinterpret_cast<const uint2*>(row)[gi];
-    const uint32_t u[4] = {w2.x & 0xffffu, w2.x >> 16, w2.y & 0xffffu, w2.y >> 16};
-    if (a.greedy) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const uint32_t v = 4u * gi + e;
-        if ((int)v >= V) continue;
-        const uint64_t cand = ((uint64_t)key16(u[e]) << 32) | (uint32_t)~v;
-        best = cand > best ? cand : best;
-      }
-    } else {
-      bool c[4], any = false;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        c[e] = 4 * gi + e < V && key16(u[e]) >= thr;
-        any |= c[e];
-      }
-      if (!any) continue;
-      uint32_t ww[4];
-      pde_rng::group_words(st, 0u, (uint64_t)b * (uint64_t)ngrp + (uint64_t)gi, ww);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (!c[e]) continue;
-        const uint32_t v = 4u * gi + e;
-        const float uu = ((float)(ww[e] >> 9) + 0.5f) * 1.1920928955078125e-07f;   // 2^-23, exact
-        const float gum = -logf(-logf(uu));
-        const float sc = bf2f(u[e]) * a.inv_temp + gum;
-        const uint64_t cand = ((uint64_t)fkey32(sc) << 32) | (uint32_t)~v;
-        best = cand > best ? cand : best;
-      }
-    }
-  }
-  best = wave_max_u64(best);
-  if ((tid & 63) == 0) bred[w] = best;
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < SM_NT / 64; ++i) best = bred[i] > best ? bred[i] : best;
-    int64_t tok = (int64_t)(uint32_t)~(uint32_t)best;
-    if (a.eos >= 0) {
-      if (fin) tok = a.eos;
-      if (tok == a.eos) a.state[PDE_DS_FIN + b] = 1;
-    }
-    a.next[b] = tok;
-    if (a.thr_out) a.thr_out[b] = (int)thr;
-    if (step >= 0 && slot >= 0 && slot < a.out_stride) a.out[(size_t)b * a.out_stride + slot] = tok;
-  }
-  if (a.logits_out && step >= 0 && step < a.max_new) {
-    bf16_t* dst = reinterpret_cast<bf16_t*>(a.logits_out) + ((size_t)b * a.max_new + step) * V;
-    for (int v = tid; v < V; v += SM_NT) dst[v] = row[v];
-  }
-}
-
-// tail of the sampler launch: every row has read the state
-__global__ void k_dec_advance(int* __restrict__ state) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    state[PDE_DS_POS] += 1;
-    state[PDE_DS_STEP] += 1;
-    state[PDE_DS_RNG + 2] = (int)((uint32_t)state[PDE_DS_RNG + 2] + 1u);
-  }
-}
+// device code shared with decode_proc.hip, which instantiates the sampler with the logit processors
+#include "decode_sample.h"
 
 }  // namespace
 

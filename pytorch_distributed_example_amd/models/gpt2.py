@@ -272,7 +272,8 @@ class GPT(tnn.Module):
     # ------------------------------------------------------------------------------- generation
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, seed=None, generator=None,
                  eos_token_id=None, use_graph=True, return_logits=False, top_p=None, prompt_lens=None,
-                 pad_token_id=0, _after_prefill=None):
+                 pad_token_id=0, _after_prefill=None, repetition_penalty=1.0, frequency_penalty=0.0,
+                 presence_penalty=0.0, logit_bias=None, suppress_tokens=None, min_new_tokens=0):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` ``[B, T0]`` (``T0 >= 1``).
 
         Returns ``[B, T0 + max_new_tokens]`` int64, and with ``return_logits`` also the logits every token
@@ -293,6 +294,17 @@ class GPT(tnn.Module):
         ``state_dict()``) or a fresh one from ``seed``; ``model.rng``, the dropout generator, is never
         touched.  A row that emits ``eos_token_id`` keeps emitting it.  Runs without gradients and with
         dropout off, and restores the module's training flag.
+
+        ``repetition_penalty`` (``> 0``, HF / vLLM: logits of tokens seen in the prompt or the output are
+        divided by it when positive, multiplied when not), ``frequency_penalty`` and ``presence_penalty``
+        (OpenAI / vLLM: ``f * count + p * [count > 0]`` is subtracted, counting generated tokens only),
+        ``logit_bias`` (fp32 ``[V]`` or ``[B, V]`` on the model's device, added; ``-inf`` bans a token),
+        ``suppress_tokens`` (token ids that never appear) and ``min_new_tokens`` (no ``eos_token_id`` before
+        that step) are the logit processors defined in ``ops/decode.py``, applied in that order before the
+        sampling above, one value for the whole batch.  On the GPU they run inside the sampler kernel on a
+        per-row history of token counts that lives on the device, so they work under graph replay.  With all
+        of them at their defaults nothing is allocated and the sampler runs as before.  ``return_logits``
+        keeps returning the raw model logits, not the processed ones.
 
         GPU (bf16, ``B <= 16``): the prompt, padded to a multiple of 128, goes through the training
         kernels once and fills the KV cache; every further token is one decode step -- about a hundred
@@ -330,6 +342,9 @@ class GPT(tnn.Module):
         if eos_token_id is not None and not 0 <= eos_token_id < cfg.vocab_size:
             raise ValueError("generate: eos_token_id must be a token of the vocabulary")
         dev = self.transformer.wte.weight.device
+        procs = D.LogitProcessors(repetition_penalty, frequency_penalty, presence_penalty, logit_bias, suppress_tokens,
+                                  min_new_tokens, eos_token_id).check(B, cfg.vocab_size, dev)
+        procs = procs if procs.active else None          # neutral settings: the calls below are what they were
         if generator is None:
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -342,31 +357,37 @@ class GPT(tnn.Module):
             with torch.no_grad():
                 run = self._generate_gpu if dev.type == "cuda" else self._generate_cpu
                 return run(idx.to(dev).long(), max_new_tokens, float(temperature), top_k, generator, eos_token_id,
-                           use_graph, return_logits, _after_prefill, top_p, lens, int(pad_token_id))
+                           use_graph, return_logits, _after_prefill, top_p, lens, int(pad_token_id), procs)
         finally:
             self.train(was_training)
 
     def _generate_cpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill,
-                      top_p=None, lens=None, pad=0):
+                      top_p=None, lens=None, pad=0, procs=None):
         V = self.config.vocab_size
         if lens is not None:
             return self._generate_cpu_ragged(idx, n_new, temperature, top_k, generator, eos, return_logits, top_p,
-                                             lens, pad)
+                                             lens, pad, procs)
         seq = idx
         fin = torch.zeros(idx.shape[0], dtype=torch.bool)
         kept = []
+        sample = None if procs is None else _CpuProcSampler(procs, idx, None, V, generator, temperature, top_k, eos,
+                                                           top_p)
         for _ in range(n_new):
             logits = self(seq)[:, -1]
-            tok = D.sample_reference(logits, V, generator.next(), temperature, top_k, top_p=top_p)
-            if eos is not None:
-                tok = torch.where(fin, torch.full_like(tok, eos), tok)
-                fin = fin | (tok == eos)
+            if sample is not None:
+                tok = sample(logits)
+            else:
+                tok = D.sample_reference(logits, V, generator.next(), temperature, top_k, top_p=top_p)
+                if eos is not None:
+                    tok = torch.where(fin, torch.full_like(tok, eos), tok)
+                    fin = fin | (tok == eos)
             seq = torch.cat([seq, tok[:, None]], dim=1)
             if return_logits:
                 kept.append(logits)
         return (seq, torch.stack(kept, dim=1)) if return_logits else seq
 
-    def _generate_cpu_ragged(self, idx, n_new, temperature, top_k, generator, eos, return_logits, top_p, lens, pad):
+    def _generate_cpu_ragged(self, idx, n_new, temperature, top_k, generator, eos, return_logits, top_p, lens, pad,
+                             procs=None):
         """One right-padded forward per token; row ``b``'s logits are row ``len_b + s - 1`` of it (causal:
         independent of what follows), gathered into ``[B, V]`` for one sampler call per step, so the
         Philox row index is ``b`` as on the GPU."""
@@ -382,12 +403,17 @@ class GPT(tnn.Module):
         seq[:, :Tl] = torch.where(real[:, :Tl], idx[:, :Tl], seq[:, :Tl])
         fin = torch.zeros(B, dtype=torch.bool)
         kept = []
+        sample = None if procs is None else _CpuProcSampler(procs, idx, lens, V, generator, temperature, top_k, eos,
+                                                           top_p)
         for s in range(n_new):
             logits = self(seq[:, :Tl + s])[rows, ln + s - 1]
-            tok = D.sample_reference(logits, V, generator.next(), temperature, top_k, top_p=top_p)
-            if eos is not None:
-                tok = torch.where(fin, torch.full_like(tok, eos), tok)
-                fin = fin | (tok == eos)
+            if sample is not None:
+                tok = sample(logits)
+            else:
+                tok = D.sample_reference(logits, V, generator.next(), temperature, top_k, top_p=top_p)
+                if eos is not None:
+                    tok = torch.where(fin, torch.full_like(tok, eos), tok)
+                    fin = fin | (tok == eos)
             seq[rows, ln + s] = tok
             out[rows, ln + s] = tok
             if return_logits:
@@ -395,9 +421,9 @@ class GPT(tnn.Module):
         return (out, torch.stack(kept, dim=1)) if return_logits else out
 
     def _generate_gpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill,
-                      top_p=None, lens=None, pad=0):
+                      top_p=None, lens=None, pad=0, procs=None):
         ses = DecodeSession(self, idx, n_new, temperature, top_k, generator.state, eos, return_logits, top_p=top_p,
-                            prompt_lens=lens, pad_token_id=pad)
+                            prompt_lens=lens, pad_token_id=pad, processors=procs)
         if _after_prefill is not None:
             _after_prefill(ses.cache)
         if n_new > 1 and use_graph:
@@ -429,6 +455,29 @@ class GPT(tnn.Module):
         return 6 * N + 6 * c.n_layer * c.n_embd * c.block_size  # causal: half of 12*L*C*T
 
 
+class _CpuProcSampler:
+    """The sampling step of the CPU generations when logit processors are on: ``ops.sample`` on a CPU
+    ``DecodeState`` and ``TokenCounts``, the path the GPU takes, so that eos, the step that ``min_new_tokens``
+    compares with and the counts are kept in one place.  Advances ``generator`` by one draw per call."""
+
+    def __init__(self, procs, idx, lens, V, generator, temperature, top_k, eos, top_p):
+        self.B, self.V, self.procs, self.generator = idx.shape[0], V, procs, generator
+        self.args = (temperature, top_k, eos)
+        self.top_p = top_p
+        self.state = D.DecodeState("cpu", generator.state)
+        self.counts = None
+        self.prompt = (idx, lens)
+
+    def __call__(self, logits):
+        if self.counts is None:          # the logits' width is the counts' width
+            self.counts = D.TokenCounts(self.B, logits.shape[1]).add_prompt(*self.prompt)
+            self.bias = self.procs.bias(self.B, self.V, logits.shape[1])
+        tok = D.sample(logits, self.V, self.state, *self.args, top_p=self.top_p, processors=self.procs,
+                       counts=self.counts, _bias=self.bias).clone()
+        self.generator.state.copy_(self.state.rng)
+        return tok
+
+
 class DecodeSession:
     """One GPU generation of ``GPT.generate``: the KV cache, the device state and the static buffers.
 
@@ -437,14 +486,29 @@ class DecodeSession:
     the longest prompt, and the device state carries every row's offset from it.  ``step()`` then generates
     one token per call and touches nothing on the host that changes between tokens, so ``capture()`` can
     record it once and every ``replay()`` of the returned graph yields the next token.  Call under
-    ``torch.no_grad()`` with the model in eval mode (``GPT.generate`` does)."""
+    ``torch.no_grad()`` with the model in eval mode (``GPT.generate`` does).
+
+    The logit processors (``processors``, an ``ops.LogitProcessors``, or the six keywords of ``GPT.generate``):
+    when any of them is on, the session allocates the token counts, the sampler's workspace and the padded
+    bias once, sets the prompt flags before the prefill's sample, and every sample passes them; the counts
+    live on the device and the sampler advances them, so a replayed step sees the history.  When none is on,
+    ``counts``, ``work`` and ``bias`` stay ``None`` and the sampler is called exactly as without them."""
 
     def __init__(self, model, idx, n_new, temperature=1.0, top_k=None, rng_state=None, eos=None,
-                 return_logits=False, top_p=None, prompt_lens=None, pad_token_id=0):
+                 return_logits=False, top_p=None, prompt_lens=None, pad_token_id=0, processors=None,
+                 repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None,
+                 suppress_tokens=None, min_new_tokens=0):
         cfg, t = model.config, model.transformer
         dev = idx.device
         B, Tin = idx.shape
         D.check_top_p(top_p, "generate")
+        if processors is None:
+            processors = D.LogitProcessors(repetition_penalty, frequency_penalty, presence_penalty, logit_bias,
+                                           suppress_tokens, min_new_tokens, eos)
+        processors.check(B, cfg.vocab_size, dev)
+        # inactive processors: no counts, no workspace, and _sample calls exactly what it called without them
+        self.processors = processors if processors.active else None
+        self.counts = self.work = self.bias = None
         if prompt_lens is None:
             lens = None
             T0 = Tin
@@ -500,10 +564,20 @@ class DecodeSession:
         self.next = torch.zeros(B, device=dev, dtype=torch.int64)
         self.logits_out = (torch.empty(B, n_new, self.V, device=dev, dtype=torch.bfloat16)
                            if return_logits else None)
+        if self.processors is not None:          # allocated once; the prompt flags before the prefill's sample
+            Vp = wte.shape[0]
+            self.counts = D.TokenCounts(B, Vp, dev).add_prompt(idx, self.state, T0=T0)
+            self.work = torch.empty(B, Vp, device=dev, dtype=torch.bfloat16)
+            self.bias = self.processors.bias(B, self.V, Vp, dev)
         self._sample(D.skinny_linear(h, wte))      # token T0; the state now points at it
 
     def _sample(self, logits):
         temperature, top_k, eos, top_p = self.sampling
+        if self.processors is not None:
+            D.sample(logits, self.V, self.state, temperature, top_k, eos, next=self.next, out=self.out,
+                     logits_out=self.logits_out, T0=self.T0, top_p=top_p, processors=self.processors,
+                     counts=self.counts, processed_out=self.work, _bias=self.bias)
+            return
         D.sample(logits, self.V, self.state, temperature, top_k, eos, next=self.next, out=self.out,
                  logits_out=self.logits_out, T0=self.T0, top_p=top_p)
 
@@ -522,6 +596,7 @@ class DecodeSession:
         the first replay)."""
         dev = self.next.device
         saved = (self.state.buf.clone(), self.next.clone())
+        counts = None if self.counts is None else self.counts.buf.clone()    # the warm-up step counts its token
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(dev)
         side.wait_stream(cur)
@@ -530,6 +605,8 @@ class DecodeSession:
         cur.wait_stream(side)
         self.state.buf.copy_(saved[0])
         self.next.copy_(saved[1])
+        if counts is not None:
+            self.counts.buf.copy_(counts)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             self.step()

@@ -30,6 +30,27 @@ Sampling definition (``sample`` on the GPU and ``sample_reference`` in numpy com
   the reference in fp64; ``p_slack`` of ``sample_reference`` says how far ``P * W`` is from the nearest
   boundary at which the two could disagree.
 
+Logit processors (``LogitProcessors``; ``sample`` on the GPU and ``process_logits_reference`` in numpy
+float32 compute the same bits).  Consider row ``b`` at generation step ``s`` (the state's step, 0 for the first
+generated token), ``x_v`` the model's logit converted to fp32, ``v < V``.  The prompt of row ``b`` is
+``idx[b, :len_b]`` and its generated tokens so far are what was written to ``out[b, len_b : len_b + s]``, eos
+forced on a finished row included.  ``TokenCounts`` holds that history on the device::
+
+    n_v    = number of times v occurs among the generated tokens of row b so far
+    seen_v = n_v > 0 or v occurs in the prompt of row b
+
+    1. repetition (r > 0, 1 = off):   if seen_v:  x = x * fp32(1 / r) if x > 0 else x * fp32(r)
+    2. frequency f, presence p:       x = (x - fp32(f) * float(n_v)) - (fp32(p) if n_v > 0 else 0)
+    3. bias (fp32 [V] or [B, V]):     x = x + bias[b, v]              (-inf bans v; +inf and NaN are rejected)
+    4. min_new_tokens m (needs eos):  if s < m and v == eos:  x = -inf
+    5. y_v = x rounded to the logits' dtype, round-to-nearest-even    (bf16 on the GPU)
+
+The order is vLLM's: repetition applies to prompt and output, frequency / presence to output only.  Every fp32
+operation is rounded on its own (no fused multiply-add); the two factors of step 1 are computed on the host;
+step 3 is skipped without a bias (``suppress_tokens`` are a bias of ``-inf``).  The sampling definition above
+then applies to ``y``, unchanged.  ``return_logits`` / ``logits_out`` keep returning the raw model logits.  A
+row whose every token is banned is the caller's error: it yields some token ``< V``.
+
 GPU tensors always run the framework kernels; an unsupported shape raises ``NotImplementedError``.
 """
 from __future__ import annotations
@@ -341,8 +362,195 @@ def key16_to_float(key):
     return np.where(k == 0, -np.inf, val)
 
 
+# --------------------------------------------------------------------------------------- logit processors
+class TokenCounts:
+    """The history the logit processors depend on: int32 ``[B, Vp]`` (layout in ``pde_decode.h``).  Bit 30 of
+    word ``(b, v)`` says that ``v`` occurs in the prompt of row ``b``; bits 0..29 count how often row ``b`` has
+    generated ``v``.  The sampler reads the buffer and adds the token it emits, so a captured decode step
+    follows the history on every replay."""
+
+    PROMPT = 1 << 30
+    COUNT = PROMPT - 1
+
+    def __init__(self, B: int, Vp: int, device=None):
+        if B < 1 or Vp < 1:
+            raise ValueError("TokenCounts: B >= 1 and Vp >= 1")
+        self.device = torch.device("cpu" if device is None else device)
+        self.buf = torch.zeros(int(B), int(Vp), dtype=torch.int32, device=self.device)
+
+    def add_prompt(self, idx, state_or_lens=None, T0=None):
+        """Set the prompt flag of every token of ``idx[b, :len_b]``.  ``state_or_lens`` is a ``DecodeState``
+        (``len_b = T0 + row offset``, read on the device; ``T0`` defaults to the width of ``idx``), a list of
+        ``B`` lengths, or ``None`` (every column).  Columns past ``len_b`` are never counted, whatever they
+        hold.  To be called before the first token is generated: the counts are zero then, which is what
+        lets the kernel store the flag word without an atomic."""
+        B, Vp = self.buf.shape
+        if idx.dim() != 2 or idx.shape[0] != B or idx.shape[1] < 1:
+            raise ValueError(f"add_prompt: idx must be [{B}, width >= 1] (got {tuple(idx.shape)})")
+        width = idx.shape[1]
+        if isinstance(state_or_lens, DecodeState):
+            state, T0 = state_or_lens, width if T0 is None else int(T0)
+        else:
+            lens = [width] * B if state_or_lens is None else [
+                int(n) for n in (state_or_lens.tolist() if torch.is_tensor(state_or_lens) else state_or_lens)]
+            if len(lens) != B or min(lens) < 0 or max(lens) > width:
+                raise ValueError(f"add_prompt: {B} lengths in 0 .. {width} (got {lens})")
+            T0 = max(lens)
+            state = None
+        if not 0 <= T0 <= width:
+            raise ValueError(f"add_prompt: 0 <= T0 <= {width} (got {T0})")
+        if self.buf.is_cuda:
+            if B > MAX_ROWS:
+                raise NotImplementedError(f"add_prompt: at most {MAX_ROWS} rows on the GPU (got {B})")
+            if state is None:
+                state = DecodeState(self.device, row_offsets=[n - T0 for n in lens])
+            idx = idx.to(self.device, torch.int64)
+            kernels().decode_count_prompt(idx if idx.is_contiguous() else idx.contiguous(), state.buf, self.buf, T0)
+            return self
+        if state is not None:
+            offs = state.row_offsets[:B].tolist() + [0] * max(B - MAX_ROWS, 0)
+            lens = [min(max(T0 + o, 0), width) for o in offs]
+        for b, n in enumerate(lens):
+            tok = idx[b, :n].long().cpu()
+            tok = tok[(tok >= 0) & (tok < Vp)]
+            self.buf[b, tok] |= self.PROMPT
+        return self
+
+    def add_(self, tok):
+        """What the sampler does after choosing: one more occurrence of ``tok[b]`` in row ``b`` (CPU ops)."""
+        rows = torch.arange(self.buf.shape[0], device=self.buf.device)
+        self.buf[rows, tok.to(self.buf.device).long()] += 1
+        return self
+
+    def seen(self):
+        """bool ``[B, Vp]``: the token occurs in the row's prompt or among its generated tokens."""
+        return self.buf != 0
+
+    def generated(self):
+        """int32 ``[B, Vp]``: how often the row has generated the token."""
+        return self.buf & self.COUNT
+
+
+def _finite(x, name):
+    x = float(x)
+    if not math.isfinite(x):
+        raise ValueError(f"LogitProcessors: {name} must be finite (got {x})")
+    return x
+
+
+class LogitProcessors:
+    """Penalties, logit bias and ``min_new_tokens`` of a generation, validated on the host (``ValueError``).
+    The definition is in the module docstring.  ``logit_bias`` is an fp32 tensor ``[V]`` or ``[B, V]`` on the
+    logits' device (``-inf`` bans a token; NaN and ``+inf`` are rejected); ``suppress_tokens`` are merged into it
+    as ``-inf``.  ``active`` is False when every setting is neutral: the sampler then runs as without processors."""
+
+    def __init__(self, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0, presence_penalty: float = 0.0,
+                 logit_bias=None, suppress_tokens=None, min_new_tokens: int = 0, eos_token_id=None):
+        self.repetition_penalty = _finite(repetition_penalty, "repetition_penalty")
+        if self.repetition_penalty <= 0:
+            raise ValueError(f"LogitProcessors: repetition_penalty must be > 0 (got {repetition_penalty})")
+        self.frequency_penalty = _finite(frequency_penalty, "frequency_penalty")
+        self.presence_penalty = _finite(presence_penalty, "presence_penalty")
+        # what the kernel is given: fp32(r), fp32(1 / r), fp32(f), fp32(p)
+        self.rep, self.inv_rep = np.float32(self.repetition_penalty), np.float32(1.0 / self.repetition_penalty)
+        self.freq, self.pres = np.float32(self.frequency_penalty), np.float32(self.presence_penalty)
+        if not (np.isfinite(self.rep) and np.isfinite(self.inv_rep) and self.rep > 0 and self.inv_rep > 0
+                and np.isfinite(self.freq) and np.isfinite(self.pres)):
+            raise ValueError("LogitProcessors: the penalties must be finite (and 1 / r > 0) in fp32")
+        if logit_bias is not None:
+            if not torch.is_tensor(logit_bias) or logit_bias.dtype != torch.float32 or logit_bias.dim() not in (1, 2):
+                raise ValueError("LogitProcessors: logit_bias must be an fp32 tensor [V] or [B, V]")
+            if bool((torch.isnan(logit_bias) | (logit_bias == math.inf)).any()):
+                raise ValueError("LogitProcessors: logit_bias holds NaN or +inf")
+        self.logit_bias = logit_bias
+        if suppress_tokens is None:
+            self.suppress_tokens = []
+        else:
+            toks = suppress_tokens.tolist() if torch.is_tensor(suppress_tokens) else list(suppress_tokens)
+            if any(int(t) != t or t < 0 for t in toks):
+                raise ValueError(f"LogitProcessors: suppress_tokens must be token ids >= 0 (got {toks})")
+            self.suppress_tokens = sorted({int(t) for t in toks})
+        if int(min_new_tokens) != min_new_tokens or min_new_tokens < 0:
+            raise ValueError(f"LogitProcessors: min_new_tokens must be an integer >= 0 (got {min_new_tokens})")
+        self.min_new_tokens = int(min_new_tokens)
+        if eos_token_id is not None and (int(eos_token_id) != eos_token_id or eos_token_id < 0):
+            raise ValueError(f"LogitProcessors: eos_token_id must be a token id >= 0 (got {eos_token_id})")
+        self.eos_token_id = None if eos_token_id is None else int(eos_token_id)
+        if self.min_new_tokens > 0 and self.eos_token_id is None:
+            raise ValueError("LogitProcessors: min_new_tokens > 0 needs eos_token_id")
+
+    @property
+    def active(self) -> bool:
+        return (self.repetition_penalty != 1.0 or self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
+                or self.logit_bias is not None or bool(self.suppress_tokens) or self.min_new_tokens > 0)
+
+    def check(self, B: int, V: int, device=None):
+        """The checks that need the batch and the vocabulary: bias shape and device, token ids ``< V``."""
+        lb = self.logit_bias
+        if lb is not None:
+            if tuple(lb.shape) not in ((V,), (B, V)):
+                raise ValueError(f"LogitProcessors: logit_bias must be [{V}] or [{B}, {V}] (got {tuple(lb.shape)})")
+            if device is not None and lb.device.type != torch.device(device).type:
+                raise ValueError(f"LogitProcessors: logit_bias is on {lb.device}, the logits are on {device}")
+        if self.suppress_tokens and self.suppress_tokens[-1] >= V:
+            raise ValueError(f"LogitProcessors: suppress_tokens outside [0, {V}) (got {self.suppress_tokens})")
+        if self.eos_token_id is not None and self.eos_token_id >= V:
+            raise ValueError(f"LogitProcessors: eos_token_id outside [0, {V}) (got {self.eos_token_id})")
+        return self
+
+    def bias(self, B: int, V: int, Vp=None, device=None):
+        """The merged bias -- ``logit_bias`` with ``-inf`` at ``suppress_tokens`` -- as fp32 ``[1 or B, Vp]`` with
+        zeros in the pad columns (``Vp`` defaults to ``V``), or ``None`` without either.  The kernel reads it with
+        aligned 16-byte loads; a generation prepares it once."""
+        self.check(B, V, device)
+        if self.logit_bias is None and not self.suppress_tokens:
+            return None
+        Vp = V if Vp is None else int(Vp)
+        dev = torch.device("cpu" if device is None else device)
+        rows = B if (self.logit_bias is not None and self.logit_bias.dim() == 2) else 1
+        buf = torch.zeros(rows, Vp, dtype=torch.float32, device=dev)
+        if self.logit_bias is not None:
+            buf[:, :V] = self.logit_bias.to(dev).reshape(rows, V)
+        if self.suppress_tokens:
+            buf[:, torch.tensor(self.suppress_tokens, dtype=torch.int64, device=dev)] = -math.inf
+        return buf
+
+
+def process_logits_reference(logits, V: int, counts, processors: LogitProcessors, step: int, _bias=None):
+    """The processors' definition (module docstring) in numpy float32, one rounded operation per line.
+    ``logits`` is ``[B, Vp]`` of any float dtype, ``counts`` a ``TokenCounts`` or its int32 ``[B, Vp]`` buffer,
+    ``step`` the generation step.  Returns ``[B, Vp]`` in the logits' dtype on the CPU: the columns ``< V``
+    processed, the pad columns as they were."""
+    if logits.dim() != 2 or not 1 <= V <= logits.shape[1]:
+        raise ValueError("process_logits_reference: logits [B, Vp] with 1 <= V <= Vp")
+    B = logits.shape[0]
+    pr = processors
+    buf = counts.buf if isinstance(counts, TokenCounts) else counts
+    if tuple(buf.shape) != tuple(logits.shape) or buf.dtype != torch.int32:
+        raise ValueError(f"process_logits_reference: counts must be int32 {tuple(logits.shape)}")
+    bias = pr.bias(B, V) if _bias is None else _bias
+    c = buf.detach().cpu().numpy()[:, :V]
+    n = c & np.int32(TokenCounts.COUNT)
+    nf = n.astype(np.float32)
+    x = logits.detach().float().cpu().numpy()[:, :V].astype(np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = np.where(c != 0, np.where(x > 0, x * pr.inv_rep, x * pr.rep), x)
+        fn = pr.freq * nf
+        x = x - fn
+        x = x - np.where(n > 0, pr.pres, np.float32(0))
+        if bias is not None:
+            x = x + bias.detach().cpu().numpy()[:, :V]
+    if int(step) < pr.min_new_tokens:
+        x[:, pr.eos_token_id] = -np.inf
+    assert x.dtype == np.float32
+    y = logits.detach().cpu().clone()
+    y[:, :V] = torch.from_numpy(np.ascontiguousarray(x)).to(logits.dtype)
+    return y
+
+
 def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=None, eos_token_id=None,
-           next=None, out=None, logits_out=None, T0: int = 0, threshold_out=None, top_p=None):
+           next=None, out=None, logits_out=None, T0: int = 0, threshold_out=None, top_p=None,
+           processors=None, counts=None, processed_out=None, _force_proc=False, _bias=None):
     """Sample one token per row of the ``[B, Vp]`` bf16 logits on the device (one block per row).
 
     With a ``DecodeState`` the launch also does the bookkeeping of a generation step: the token goes to
@@ -353,13 +561,35 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
     threshold (top-k, raised by ``top_p``) as the kernel's order-preserving 16-bit key (``key16_to_float``
     decodes it).  ``top_p`` of ``None`` or 1.0 runs the sampler without the nucleus stage.  With a plain
     4-word RNG snapshot a temporary state is used.  Returns ``next``.
-    CPU tensors run ``sample_reference`` (with the same bookkeeping on a ``DecodeState``)."""
+
+    ``processors`` (a ``LogitProcessors``) with ``counts`` (the ``TokenCounts`` of the generation) applies the
+    logit processors of the module docstring at the state's step before sampling, and adds the emitted token
+    (the eos forced on a finished row included) to ``counts``.  ``processed_out`` (``[B, Vp]`` in the logits'
+    dtype) receives the processed logits ``y``; on the GPU it is the kernel's workspace and all ``Vp`` columns are
+    written.  ``logits_out`` receives the raw logits all the same.  Processors whose ``active`` is False run the
+    sampler exactly as without them.  Their ``eos_token_id`` stands in for a missing ``eos_token_id`` here.
+    CPU tensors run ``process_logits_reference`` and ``sample_reference`` (with the same bookkeeping on a
+    ``DecodeState``)."""
     if temperature < 0:
         raise ValueError("temperature must be >= 0")
     if top_k is not None and top_k < 1:
         raise ValueError("top_k must be >= 1")
     nucleus = check_top_p(top_p, "sample")
     B = logits.shape[0]
+    proc = processors is not None and (processors.active or bool(_force_proc))
+    if proc:
+        if not isinstance(counts, TokenCounts) or tuple(counts.buf.shape) != tuple(logits.shape) \
+                or counts.buf.device != logits.device:
+            raise ValueError("sample: processors need `counts`, a TokenCounts [B, Vp] on the logits' device")
+        if eos_token_id is None:
+            eos_token_id = processors.eos_token_id
+        elif processors.min_new_tokens > 0 and int(eos_token_id) != processors.eos_token_id:
+            raise ValueError("sample: eos_token_id differs from the processors' eos_token_id")
+        bias = processors.bias(B, V, logits.shape[1], logits.device) if _bias is None else _bias
+        if processed_out is not None and (tuple(processed_out.shape) != tuple(logits.shape)
+                                          or processed_out.dtype != logits.dtype
+                                          or processed_out.device != logits.device):
+            raise ValueError("sample: processed_out must match the logits' shape, dtype and device")
     if isinstance(snapshot_or_state, DecodeState):
         state = snapshot_or_state
     else:
@@ -370,8 +600,13 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
         out = torch.zeros(B, T0 + 1, device=logits.device, dtype=torch.int64)
     eos = -1 if eos_token_id is None else int(eos_token_id)
     if not logits.is_cuda:
-        tok = sample_reference(logits, V, state, temperature, top_k, top_p=top_p)
         step = state.step()
+        y = logits
+        if proc:
+            y = process_logits_reference(logits, V, counts, processors, step, _bias=bias)
+            if processed_out is not None:
+                processed_out.copy_(y)
+        tok = sample_reference(y, V, state, temperature, top_k, top_p=top_p)
         if eos >= 0:
             fin = state.finished[:B].bool()
             tok = torch.where(fin, torch.full_like(tok, eos), tok)
@@ -382,6 +617,8 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
                 out[b, T0 + off + step] = tok[b]
         if logits_out is not None and step < logits_out.shape[1]:
             logits_out[:, step] = logits[:, :V].to(logits_out.dtype)
+        if proc:
+            counts.add_(tok)
         state.advance_()
         return next
     if logits.dim() != 2 or logits.dtype != _BF16 or logits.shape[1] % 8 or not logits.is_contiguous():
@@ -390,6 +627,14 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
         raise NotImplementedError(f"sample: at most {MAX_ROWS} rows on the GPU (got {B})")
     greedy = temperature == 0
     inv_temp = 0.0 if greedy else float(np.float32(1.0 / temperature))
+    if proc:
+        work = torch.empty_like(logits) if processed_out is None else processed_out
+        kernels().decode_sample_proc(logits, int(V), state.buf, next, out, logits_out, int(T0), inv_temp, greedy,
+                                     0 if top_k is None else int(top_k), eos, threshold_out,
+                                     float(top_p) if nucleus else 0.0, counts.buf, bias, work,
+                                     float(processors.rep), float(processors.inv_rep), float(processors.freq),
+                                     float(processors.pres), processors.min_new_tokens)
+        return next
     kernels().decode_sample(logits, int(V), state.buf, next, out, logits_out, int(T0), inv_temp, greedy,
                             0 if top_k is None else int(top_k), eos, threshold_out,
                             float(top_p) if nucleus else 0.0)

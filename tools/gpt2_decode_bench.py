@@ -19,10 +19,12 @@ Sampling is temperature 1.0 with ``--top-k`` (default 50, 0: none) and ``--top-p
 ``--context``), so the rows sit at different positions; the K / V bytes are then those of the rows' own
 contexts.  ``--sampler-reps N`` also times the sampler launch alone (``k_sample`` and its one-thread tail) on
 the logits of the prefill: N back-to-back calls between one event pair, with the run's settings and with
-top-p off.
+top-p off.  ``--penalties`` adds a second row per batch size, from the same process and prompt: the same step
+with the logit processors on (``repetition_penalty`` 1.3, ``frequency_penalty`` 0.3, ``presence_penalty`` 0.5 and
+a ``[V]`` logit bias), and under ``--sampler-reps`` the sampler launch with them (the ``PROC`` instantiation).
 
     python tools/gpt2_decode_bench.py [--context 512] [--window 64] [--rounds 5] [--batch-sizes 1 16]
-                                      [--top-k 50] [--top-p P] [--ragged] [--sampler-reps N]
+                                      [--top-k 50] [--top-p P] [--ragged] [--sampler-reps N] [--penalties]
 """
 import argparse
 import json
@@ -52,33 +54,45 @@ def prompt_lens(B, context):
     return [context] if B == 1 else [1 + round(b * (context - 1) / (B - 1)) for b in range(B)]
 
 
-def bench_sampler(B, cfg, top_k, top_p, reps, dev):
+def penalty_processors(cfg, dev):
+    """The processors of the ``--penalties`` row"""
+    bias = 0.5 * torch.randn(cfg.vocab_size, device=dev, generator=torch.Generator(dev).manual_seed(7))
+    return D.LogitProcessors(repetition_penalty=1.3, frequency_penalty=0.3, presence_penalty=0.5, logit_bias=bias)
+
+
+def bench_sampler(B, cfg, top_k, top_p, reps, dev, procs=None):
     """us per sampler launch (k_sample + tail), ``reps`` calls between one event pair"""
     logits = (torch.randn(B, cfg.padded_vocab, device=dev) * 3).to(torch.bfloat16)
     state = D.DecodeState(dev, DeviceRNG(0, device=dev).state)
     nxt = torch.zeros(B, device=dev, dtype=torch.int64)
     out = torch.zeros(B, 1, device=dev, dtype=torch.int64)
+    kw = {}
+    if procs is not None:            # buffers allocated once, as a generation does
+        kw = dict(processors=procs, counts=D.TokenCounts(B, cfg.padded_vocab, dev),
+                  processed_out=torch.empty_like(logits), _bias=procs.bias(B, cfg.vocab_size, cfg.padded_vocab, dev))
     for _ in range(10):
-        D.sample(logits, cfg.vocab_size, state, 1.0, top_k, next=nxt, out=out, top_p=top_p)
+        D.sample(logits, cfg.vocab_size, state, 1.0, top_k, next=nxt, out=out, top_p=top_p, **kw)
     e0, e1 = events(1)[0]
     torch.cuda.synchronize()
     e0.record()
     for _ in range(reps):
-        D.sample(logits, cfg.vocab_size, state, 1.0, top_k, next=nxt, out=out, top_p=top_p)
+        D.sample(logits, cfg.vocab_size, state, 1.0, top_k, next=nxt, out=out, top_p=top_p, **kw)
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
-def bench_decode(model, idx, a, lens=None):
+def bench_decode(model, idx, a, lens=None, procs=None):
     ses = DecodeSession(model, idx, a.window + 1, 1.0, a.top_k or None, DeviceRNG(0, device=idx.device).state,
-                        top_p=a.top_p, prompt_lens=lens)
+                        top_p=a.top_p, prompt_lens=lens, processors=procs)
     graph = ses.capture()
-    start = (ses.state.buf.clone(), ses.next.clone())
+    start = (ses.state.buf.clone(), ses.next.clone(), None if ses.counts is None else ses.counts.buf.clone())
 
     def rewind():
         ses.state.buf.copy_(start[0])
         ses.next.copy_(start[1])
+        if start[2] is not None:
+            ses.counts.buf.copy_(start[2])
 
     per_replay, per_window, eager = [], [], []
     for r in range(a.rounds + 1):                       # round 0 is warm-up
@@ -130,6 +144,7 @@ def main():
     ap.add_argument("--top-p", type=float, default=None, help="nucleus mass in (0, 1]; default: off")
     ap.add_argument("--ragged", action="store_true", help="prompt lengths spread from 1 to --context")
     ap.add_argument("--sampler-reps", type=int, default=0, help="also time the sampler launch alone")
+    ap.add_argument("--penalties", action="store_true", help="a second row per batch size with the logit processors on")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("gpt2_decode_bench: needs a GPU (no CPU fallback: a CPU time says nothing about the kernels)")
@@ -142,33 +157,36 @@ def main():
             idx = torch.randint(0, cfg.vocab_size, (B, a.context), device=dev,
                                 generator=torch.Generator(dev).manual_seed(B))
             lens = prompt_lens(B, a.context) if a.ragged else None
-            per_replay, per_window, eager = bench_decode(model, idx, a, lens)
-            rec = bench_recompute(model, idx, a.recompute_reps) if a.recompute_reps > 0 else None
+            rec = None
             # keys read at positions len .. len + window - 1, summed over the rows
             mean_keys = sum(n + (a.window + 1) / 2.0 for n in (lens or [a.context] * B))
             kv_bytes = cfg.n_layer * 2 * cfg.n_head * mean_keys * 64 * 2
-            extra = {"top_k": a.top_k, "top_p": a.top_p, "prompt_lens": lens}
-            if a.sampler_reps > 0:
-                extra["sampler_us_per_launch"] = {
-                    "this_run": round(bench_sampler(B, cfg, a.top_k or None, a.top_p, a.sampler_reps, dev), 2),
-                    "top_p_off": round(bench_sampler(B, cfg, a.top_k or None, None, a.sampler_reps, dev), 2)}
-            ms = statistics.median(per_replay)
-            bps = (weight_bytes + kv_bytes) / (ms * 1e-3)
-            print(json.dumps({
-                "metric": "gpt2_small_decode_ms_per_token", "batch_size": B, "context": a.context,
-                "window": a.window, "rounds": a.rounds,
-                "decode_graph_ms_per_token": {"median": round(ms, 4), "min": round(min(per_replay), 4),
-                                              "max": round(max(per_replay), 4),
-                                              "window_mean_median": round(statistics.median(per_window), 4)},
-                "decode_eager_ms_per_token_median": round(statistics.median(eager), 4),
-                "recompute_forward_ms_per_token": rec and {"median": round(statistics.median(rec), 4),
-                                                           "min": round(min(rec), 4), "max": round(max(rec), 4)},
-                "speedup_vs_recompute": rec and round(statistics.median(rec) / ms, 2),
-                "tokens_per_s_decode": round(B / (ms * 1e-3), 1),
-                "bytes_per_token": {"weights": weight_bytes, "kv": int(kv_bytes)},
-                "achieved_bytes_per_s": round(bps, 1),
-                "share_of_6.29TBps": round(bps / HBM_BYTES_PER_S, 4), **extra}), flush=True)
-
+            for procs in [None] + ([penalty_processors(cfg, dev)] if a.penalties else []):
+                per_replay, per_window, eager = bench_decode(model, idx, a, lens, procs)
+                if procs is None and a.recompute_reps > 0:       # once per batch size, after the plain row
+                    rec = bench_recompute(model, idx, a.recompute_reps)
+                extra ={"top_k": a.top_k, "top_p": a.top_p, "prompt_lens": lens, "penalties": procs is not None}
+                if a.sampler_reps > 0:
+                    k = a.top_k or None
+                    extra["sampler_us_per_launch"] = {
+                        "this_run": round(bench_sampler(B, cfg, k, a.top_p, a.sampler_reps, dev, procs), 2),
+                        "top_p_off": round(bench_sampler(B, cfg, k, None, a.sampler_reps, dev, procs), 2)}
+                ms = statistics.median(per_replay)
+                bps = (weight_bytes + kv_bytes) / (ms * 1e-3)
+                print(json.dumps({
+                    "metric": "gpt2_small_decode_ms_per_token", "batch_size": B, "context": a.context,
+                    "window": a.window, "rounds": a.rounds,
+                    "decode_graph_ms_per_token": {"median": round(ms, 4), "min": round(min(per_replay), 4),
+                                                  "max": round(max(per_replay), 4),
+                                                  "window_mean_median": round(statistics.median(per_window), 4)},
+                    "decode_eager_ms_per_token_median": round(statistics.median(eager), 4),
+                    "recompute_forward_ms_per_token": rec and {"median": round(statistics.median(rec), 4),
+                                                               "min": round(min(rec), 4), "max": round(max(rec), 4)},
+                    "speedup_vs_recompute": rec and round(statistics.median(rec) / ms, 2),
+                    "tokens_per_s_decode": round(B / (ms * 1e-3), 1),
+                    "bytes_per_token": {"weights": weight_bytes, "kv": int(kv_bytes)},
+                    "achieved_bytes_per_s": round(bps, 1),
+                    "share_of_6.29TBps": round(bps / HBM_BYTES_PER_S, 4), **extra}), flush=True)
 
 if __name__ == "__main__":
     main()
