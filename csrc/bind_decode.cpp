@@ -100,7 +100,7 @@ void decode_embed(const at::Tensor& tok, const at::Tensor& wte, const at::Tensor
             "decode_embed");
 }
 
-// the checked arguments shared by both sampler entries
+// the checked arguments shared by the sampler entries
 PdeSample sample_args(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next,
                       const at::Tensor& out, const OptT& logits_out, int64_t T0, double inv_temp, bool greedy,
                       int64_t top_k, int64_t eos, const OptT& thr_out, double top_p) {
@@ -155,13 +155,9 @@ void sample(const at::Tensor& logits, int64_t V, const at::Tensor& state, const 
 
 // The sampler with the logit processors (PdeSampleProc in pde_decode.h).  counts: int32 [B, Vp]; bias: fp32
 // [1 or B, Vp] or None; work: bf16 [B, Vp], receives the processed logits; rep / inv_rep: fp32(r), fp32(1 / r).
-void sample_proc(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next,
-                 const at::Tensor& out, const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k,
-                 int64_t eos, const OptT& thr_out, double top_p, const at::Tensor& counts, const OptT& bias,
-                 const at::Tensor& work, double rep, double inv_rep, double freq, double pres, int64_t min_new) {
-  const PdeSample a = sample_args(logits, V, state, next, out, logits_out, T0, inv_temp, greedy, top_k, eos, thr_out,
-                                  top_p);
-  const int64_t B = a.B, Vp = a.Vp;
+PdeSampleProc proc_args(const PdeSample& a, const at::Tensor& logits, const at::Tensor& counts, const OptT& bias,
+                        const at::Tensor& work, double rep, double inv_rep, double freq, double pres, int64_t min_new) {
+  const int64_t B = a.B, Vp = a.Vp, eos = a.eos;
   check_cuda(counts, "counts", I32, B * Vp);
   TORCH_CHECK(counts.dim() == 2 && counts.size(0) == B && counts.size(1) == Vp, "sample: counts must be [B, Vp]");
   check_al16(counts, "counts");
@@ -189,7 +185,53 @@ void sample_proc(const at::Tensor& logits, int64_t V, const at::Tensor& state, c
   p.inv_rep = (float)inv_rep;
   p.freq = (float)freq;
   p.pres = (float)pres;
+  return p;
+}
+
+void sample_proc(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next,
+                 const at::Tensor& out, const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k,
+                 int64_t eos, const OptT& thr_out, double top_p, const at::Tensor& counts, const OptT& bias,
+                 const at::Tensor& work, double rep, double inv_rep, double freq, double pres, int64_t min_new) {
+  const PdeSample a = sample_args(logits, V, state, next, out, logits_out, T0, inv_temp, greedy, top_k, eos, thr_out,
+                                  top_p);
+  const PdeSampleProc p = proc_args(a, logits, counts, bias, work, rep, inv_rep, freq, pres, min_new);
   hip_check(pde_sample_proc(a, p, cur_stream()), "sample");
+}
+
+// a packed sequence table (PdeSampleHist in pde_decode.h): int32 [count + 1 offsets][tokens], or None with count 0
+const int* seq_table(const OptT& t, int64_t count, const char* name) {
+  TORCH_CHECK(count >= 0 && count <= PDE_HIST_MAX_SEQS, "sample: ", name, " holds 0 .. ", PDE_HIST_MAX_SEQS,
+              " sequences, got ", count);
+  if (count == 0) return nullptr;
+  TORCH_CHECK(t.has_value() && t->defined(), "sample: ", name, " is missing");
+  check_cuda(*t, name, I32);
+  TORCH_CHECK(t->dim() == 1 && t->numel() >= 2 * count + 1, "sample: ", name, " must be [count + 1 offsets][tokens]");
+  return ptr<int>(*t);
+}
+
+// The sampler with the history constraints on top of the processors (PdeSampleHist in pde_decode.h).  ban / stop:
+// packed int32 sequence tables or None; stop_hit: int32 [B], needed with stop sequences.
+void sample_hist(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next,
+                 const at::Tensor& out, const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k,
+                 int64_t eos, const OptT& thr_out, double top_p, const at::Tensor& counts, const OptT& bias,
+                 const at::Tensor& work, double rep, double inv_rep, double freq, double pres, int64_t min_new,
+                 int64_t ngram, const OptT& ban, int64_t n_ban, const OptT& stop, int64_t n_stop,
+                 const OptT& stop_hit) {
+  const PdeSample a = sample_args(logits, V, state, next, out, logits_out, T0, inv_temp, greedy, top_k, eos, thr_out,
+                                  top_p);
+  const PdeSampleProc p = proc_args(a, logits, counts, bias, work, rep, inv_rep, freq, pres, min_new);
+  TORCH_CHECK(out.is_contiguous(), "sample: out must be contiguous");
+  TORCH_CHECK(ngram >= 0 && ngram <= PDE_HIST_MAX_NGRAM, "sample: no_repeat_ngram_size in 0 .. ", PDE_HIST_MAX_NGRAM,
+              ", got ", ngram);
+  PdeSampleHist h{};
+  h.n = (int)ngram;
+  h.ban = seq_table(ban, n_ban, "the banned sequences");
+  h.stop = seq_table(stop, n_stop, "the stop sequences");
+  h.n_ban = (int)n_ban;
+  h.n_stop = (int)n_stop;
+  h.stop_hit = optr<int>(stop_hit, "stop_hit", I32, a.B);
+  TORCH_CHECK(n_stop == 0 || (h.stop_hit != nullptr && eos >= 0), "sample: stop sequences need stop_hit and eos");
+  hip_check(pde_sample_hist(a, p, h, cur_stream()), "sample");
 }
 
 // counts[b, idx[b, t]] = prompt flag for t < T0 + the state's offset of row b; idx: int64 [B, width]
@@ -225,6 +267,11 @@ void register_decode(pybind11::module& m) {
         py::arg("out"), py::arg("logits_out"), py::arg("T0"), py::arg("inv_temp"), py::arg("greedy"), py::arg("top_k"),
         py::arg("eos"), py::arg("thr_out"), py::arg("top_p"), py::arg("counts"), py::arg("bias"), py::arg("work"),
         py::arg("rep"), py::arg("inv_rep"), py::arg("freq"), py::arg("pres"), py::arg("min_new"));
+  m.def("decode_sample_hist", &sample_hist, py::arg("logits"), py::arg("V"), py::arg("state"), py::arg("next"),
+        py::arg("out"), py::arg("logits_out"), py::arg("T0"), py::arg("inv_temp"), py::arg("greedy"), py::arg("top_k"),
+        py::arg("eos"), py::arg("thr_out"), py::arg("top_p"), py::arg("counts"), py::arg("bias"), py::arg("work"),
+        py::arg("rep"), py::arg("inv_rep"), py::arg("freq"), py::arg("pres"), py::arg("min_new"), py::arg("ngram"),
+        py::arg("ban"), py::arg("n_ban"), py::arg("stop"), py::arg("n_stop"), py::arg("stop_hit"));
   m.def("decode_count_prompt", &count_prompt);
   m.attr("DECODE_STATE_WORDS") = PDE_DS_WORDS;
 }

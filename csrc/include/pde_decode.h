@@ -96,6 +96,28 @@ typedef struct PdeSampleProc {
 } PdeSampleProc;
 hipError_t pde_sample_proc(PdeSample a, PdeSampleProc p, hipStream_t st);
 
+// The history constraints of a sampler launch, on top of the logit processors.  Row b's history is
+// h[0 .. L-1] = out[b, 0 : L] with L = len_b + step, len_b = T0 + state[PDE_DS_OFF + b], both from the state.
+// A sequence table is packed int32: [count + 1 offsets][tokens], sequence q = tokens[offsets[q] .. offsets[q + 1]).
+//   n-gram (n >= 1, L >= n - 1):  v is banned iff h[j-n+1 .. j-1] == h[L-n+1 .. L-1] and h[j] == v for some
+//                                 n - 1 <= j <= L - 1
+//   banned sequence of m tokens:  seq[m-1] is banned iff L >= m - 1 and h[L-m+1 .. L-1] == seq[0 .. m-2]
+//   a ban:                        y = -inf, after the bias and before the sampling; a finished row has none
+//   stop sequence of m tokens:    a row that was not finished and emits `tok` at step s becomes finished, and
+//                                 stop_hit[b] = the lowest such q, iff s + 1 >= m and
+//                                 out[b, len_b+s-m+1 .. len_b+s] == seq with tok in place (needs eos >= 0)
+// Tokens outside [0, V) ban nothing.  Nothing is read from `out` at or past L.
+#define PDE_HIST_MAX_NGRAM 8
+#define PDE_HIST_MAX_SEQS 256          // per table
+typedef struct PdeSampleHist {
+  const int* ban;       // table of banned sequences, or null with n_ban == 0
+  const int* stop;      // table of stop sequences, or null with n_stop == 0
+  int* stop_hit;        // [B]; needed with n_stop > 0
+  int n;                // no_repeat_ngram_size, 0: off
+  int n_ban, n_stop;
+} PdeSampleHist;
+hipError_t pde_sample_hist(PdeSample a, PdeSampleProc p, PdeSampleHist h, hipStream_t st);
+
 // counts[b, idx[b, t]] = PDE_TC_PROMPT for t < len_b = T0 + state[PDE_DS_OFF + b] (clamped to [0, width]); idx is
 // [B, width] with row stride `stride`.  To be called on zeroed counts: duplicates store the same word, so the
 // stores need no atomic.  Tokens outside [0, Vp) are skipped.

@@ -1,6 +1,7 @@
 // The device-side sampler of the GPT-2 decode step: device code shared by two translation units.
 // decode.hip instantiates the plain sampler (k_sample<TOPP>), decode_proc.hip the one with the logit processors
-// (k_sample<TOPP, PdeSampleProc>).  They are compiled apart on purpose: in one unit the extra instantiations
+// (k_sample<TOPP, PdeSampleProc>), decode_hist.hip the one with the history constraints on top of them
+// (k_sample<TOPP, PdeSampleProc, PdeSampleHist>).  They are compiled apart on purpose: in one unit the extra instantiations
 // changed how the compiler inlined and unswitched the nucleus stage of the plain top-p sampler, and a generation
 // without processors is to run the instruction streams it ran before.  Include inside the unit's anonymous
 // namespace, after pde_hip.h, pde_bf16.h, pde_decode.h and pde_rng.h.
@@ -203,12 +204,24 @@ __device__ __forceinline__ float proc_logit(float x, int c, float bias, bool has
 // `row` is that workspace row: every pass below runs on y as it runs on the raw logits.  The prologue is the
 // block's only reader of its counts row, so thread 0 can add the emitted token with a plain load and store at
 // the end.  logits_out keeps copying the raw row.
+// HIST (a third struct, PdeSampleHist, on top of PROC) adds the history constraints of pde_decode.h.  The row's
+// history is out[b, 0 : L], L = len_b + step, both from the state.  After the prologue's barrier the block walks
+// the history: thread j compares the n - 1 tokens before position j with the last n - 1 and stores bf16 -inf to
+// y[h[j]] on a match (every writer stores the same value: no atomic), one thread per banned sequence compares its
+// head with the history's tail and bans its last token, and a second barrier makes y final for the passes.  In
+// the tail wave 0 matches the stop sequences against the generated tokens with the emitted one in place, one
+// sequence per lane and round, and a wave minimum picks the lowest index.  Nothing reads `out` at or past L.
 __device__ __forceinline__ const PdeSampleProc& proc_args(const PdeSampleProc& p) { return p; }
+__device__ __forceinline__ const PdeSampleProc& proc_args(const PdeSampleProc& p, const PdeSampleHist&) { return p; }
+__device__ __forceinline__ const PdeSampleHist& hist_args(const PdeSampleProc&, const PdeSampleHist& h) { return h; }
 template <bool TOPP, typename... Proc>
 __global__ __launch_bounds__(SM_NT) void k_sample(PdeSample a, Proc... proc) {
-  constexpr bool PROC = sizeof...(Proc) == 1;
+  constexpr bool PROC = sizeof...(Proc) >= 1;
+  constexpr bool HIST = sizeof...(Proc) == 2;
   [[maybe_unused]] PdeSampleProc p{};
   if constexpr (PROC) p = proc_args(proc...);
+  [[maybe_unused]] PdeSampleHist hc{};
+  if constexpr (HIST) hc = hist_args(proc...);
   __shared__ uint32_t hist[4][256];
   __shared__ uint32_t sel[2];
   __shared__ uint64_t bred[SM_NT / 64];
@@ -245,6 +258,38 @@ __global__ __launch_bounds__(SM_NT) void k_sample(PdeSample a, Proc... proc) {
     }
     __syncthreads();            // the row of y, written by the whole block, is read by the whole block
     row = y;
+  }
+
+  // history constraints: slot = len_b + step is the history's length L.  A state that points outside `out`
+  // switches them off; a finished row emits eos whatever is banned, so its y stays as the processors left it.
+  [[maybe_unused]] bool hist_on = false;
+  [[maybe_unused]] const int64_t* h = nullptr;
+  if constexpr (HIST) {
+    hist_on = step >= 0 && slot >= step && slot <= a.out_stride && !(a.eos >= 0 && fin);
+    h = a.out + (size_t)b * a.out_stride;
+    if (hist_on) {
+      const int L = slot, n = hc.n;
+      bf16_t* y = reinterpret_cast<bf16_t*>(p.work) + (size_t)b * a.Vp;
+      const bf16_t ninf = f2bf(-INFINITY);
+      if (n >= 1 && L >= n - 1) {
+        for (int j = n - 1 + tid; j < L; j += SM_NT) {
+          bool eq = true;
+          for (int i = 1; i < n; ++i) eq &= h[j - i] == h[L - i];
+          const int64_t v = h[j];
+          if (eq && v >= 0 && v < V) y[v] = ninf;
+        }
+      }
+      for (int q = tid; q < hc.n_ban; q += SM_NT) {
+        const int o0 = hc.ban[q], m = hc.ban[q + 1] - o0;
+        const int* seq = hc.ban + hc.n_ban + 1 + o0;
+        if (m < 1 || L < m - 1) continue;
+        bool eq = true;
+        for (int i = 0; i < m - 1; ++i) eq &= h[L - m + 1 + i] == (int64_t)seq[i];
+        const int v = seq[m - 1];
+        if (eq && v >= 0 && v < V) y[v] = ninf;
+      }
+    }
+    __syncthreads();            // the bans, stored by any thread, are read by the whole block
   }
 
   uint32_t thr = 0;             // candidates: key16 >= thr
@@ -323,12 +368,47 @@ __global__ __launch_bounds__(SM_NT) void k_sample(PdeSample a, Proc... proc) {
   best = wave_max_u64(best);
   if ((tid & 63) == 0) bred[w] = best;
   __syncthreads();
+  [[maybe_unused]] int hit = -1;  // lowest index of a stop sequence that ends at the token emitted now
+  if constexpr (HIST) {
+    // hist_on: the row was not finished, so the token is the block's best.  Every lane of wave 0 holds wave 0's
+    // maximum after the xor reduction and reads the other waves' from LDS.
+    if (w == 0 && hist_on && a.eos >= 0 && hc.n_stop > 0) {
+      uint64_t bb = best;
+      for (int i = 1; i < SM_NT / 64; ++i) bb = bred[i] > bb ? bred[i] : bb;
+      const int64_t tok = (int64_t)(uint32_t)~(uint32_t)bb;
+      const int L = slot;
+      int mine = 0x7fffffff;
+      for (int q = tid; q < hc.n_stop; q += 64) {
+        const int o0 = hc.stop[q], m = hc.stop[q + 1] - o0;
+        const int* seq = hc.stop + hc.n_stop + 1 + o0;
+        if (m < 1 || step + 1 < m) continue;                 // the match lies in the generated tokens
+        bool eq = tok == (int64_t)seq[m - 1];
+        for (int i = 0; i < m - 1; ++i) eq &= h[L - m + 1 + i] == (int64_t)seq[i];
+        if (eq) {
+          mine = q;
+          break;
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const int t = __shfl_xor(mine, o, 64);
+        mine = t < mine ? t : mine;
+      }
+      if (mine != 0x7fffffff) hit = mine;
+    }
+  }
   if (tid == 0) {
     for (int i = 1; i < SM_NT / 64; ++i) best = bred[i] > best ? bred[i] : best;
     int64_t tok = (int64_t)(uint32_t)~(uint32_t)best;
     if (a.eos >= 0) {
       if (fin) tok = a.eos;
       if (tok == a.eos) a.state[PDE_DS_FIN + b] = 1;
+    }
+    if constexpr (HIST) {
+      if (hit >= 0) {
+        a.state[PDE_DS_FIN + b] = 1;
+        hc.stop_hit[b] = hit;
+      }
     }
     a.next[b] = tok;
     if (a.thr_out) a.thr_out[b] = (int)thr;

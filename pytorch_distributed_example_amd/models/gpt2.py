@@ -273,7 +273,8 @@ class GPT(tnn.Module):
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, seed=None, generator=None,
                  eos_token_id=None, use_graph=True, return_logits=False, top_p=None, prompt_lens=None,
                  pad_token_id=0, _after_prefill=None, repetition_penalty=1.0, frequency_penalty=0.0,
-                 presence_penalty=0.0, logit_bias=None, suppress_tokens=None, min_new_tokens=0):
+                 presence_penalty=0.0, logit_bias=None, suppress_tokens=None, min_new_tokens=0,
+                 no_repeat_ngram_size=0, bad_words_ids=None, stop_sequences=None):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` ``[B, T0]`` (``T0 >= 1``).
 
         Returns ``[B, T0 + max_new_tokens]`` int64, and with ``return_logits`` also the logits every token
@@ -305,6 +306,14 @@ class GPT(tnn.Module):
         per-row history of token counts that lives on the device, so they work under graph replay.  With all
         of them at their defaults nothing is allocated and the sampler runs as before.  ``return_logits``
         keeps returning the raw model logits, not the processed ones.
+
+        ``no_repeat_ngram_size`` (``n`` in 1 .. 8: no n-gram occurs twice in a row's prompt plus output, as Hugging
+        Face's processor), ``bad_words_ids`` (token lists that never appear as a sequence; a single token is never
+        emitted) and ``stop_sequences`` (token lists; a row whose generated tokens end in one becomes finished and
+        emits ``eos_token_id``, which they need, from the next step on; the sequence stays in the output) are the
+        history constraints defined in ``ops/decode.py``.  They match each row's history -- its columns of the
+        output buffer -- inside the sampler kernel, so they too work under graph replay, and with all three at
+        their defaults nothing changes.  Bans apply after the bias and before ``min_new_tokens``.
 
         GPU (bf16, ``B <= 16``): the prompt, padded to a multiple of 128, goes through the training
         kernels once and fills the KV cache; every further token is one decode step -- about a hundred
@@ -345,6 +354,9 @@ class GPT(tnn.Module):
         procs = D.LogitProcessors(repetition_penalty, frequency_penalty, presence_penalty, logit_bias, suppress_tokens,
                                   min_new_tokens, eos_token_id).check(B, cfg.vocab_size, dev)
         procs = procs if procs.active else None          # neutral settings: the calls below are what they were
+        hist = D.HistoryConstraints(no_repeat_ngram_size, bad_words_ids, stop_sequences,
+                                    eos_token_id).check(cfg.vocab_size)
+        hist = hist if hist.active else None
         if generator is None:
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -357,21 +369,22 @@ class GPT(tnn.Module):
             with torch.no_grad():
                 run = self._generate_gpu if dev.type == "cuda" else self._generate_cpu
                 return run(idx.to(dev).long(), max_new_tokens, float(temperature), top_k, generator, eos_token_id,
-                           use_graph, return_logits, _after_prefill, top_p, lens, int(pad_token_id), procs)
+                           use_graph, return_logits, _after_prefill, top_p, lens, int(pad_token_id), procs, hist)
         finally:
             self.train(was_training)
 
     def _generate_cpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill,
-                      top_p=None, lens=None, pad=0, procs=None):
+                      top_p=None, lens=None, pad=0, procs=None, hist=None):
         V = self.config.vocab_size
         if lens is not None:
             return self._generate_cpu_ragged(idx, n_new, temperature, top_k, generator, eos, return_logits, top_p,
-                                             lens, pad, procs)
+                                             lens, pad, procs, hist)
         seq = idx
         fin = torch.zeros(idx.shape[0], dtype=torch.bool)
         kept = []
-        sample = None if procs is None else _CpuProcSampler(procs, idx, None, V, generator, temperature, top_k, eos,
-                                                           top_p)
+        sample = None
+        if procs is not None or hist is not None:
+            sample = _CpuProcSampler(procs, idx, None, V, generator, temperature, top_k, eos, top_p, hist, n_new)
         for _ in range(n_new):
             logits = self(seq)[:, -1]
             if sample is not None:
@@ -387,7 +400,7 @@ class GPT(tnn.Module):
         return (seq, torch.stack(kept, dim=1)) if return_logits else seq
 
     def _generate_cpu_ragged(self, idx, n_new, temperature, top_k, generator, eos, return_logits, top_p, lens, pad,
-                             procs=None):
+                             procs=None, hist=None):
         """One right-padded forward per token; row ``b``'s logits are row ``len_b + s - 1`` of it (causal:
         independent of what follows), gathered into ``[B, V]`` for one sampler call per step, so the
         Philox row index is ``b`` as on the GPU."""
@@ -403,8 +416,9 @@ class GPT(tnn.Module):
         seq[:, :Tl] = torch.where(real[:, :Tl], idx[:, :Tl], seq[:, :Tl])
         fin = torch.zeros(B, dtype=torch.bool)
         kept = []
-        sample = None if procs is None else _CpuProcSampler(procs, idx, lens, V, generator, temperature, top_k, eos,
-                                                           top_p)
+        sample = None
+        if procs is not None or hist is not None:
+            sample = _CpuProcSampler(procs, idx, lens, V, generator, temperature, top_k, eos, top_p, hist, n_new)
         for s in range(n_new):
             logits = self(seq[:, :Tl + s])[rows, ln + s - 1]
             if sample is not None:
@@ -421,9 +435,9 @@ class GPT(tnn.Module):
         return (out, torch.stack(kept, dim=1)) if return_logits else out
 
     def _generate_gpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill,
-                      top_p=None, lens=None, pad=0, procs=None):
+                      top_p=None, lens=None, pad=0, procs=None, hist=None):
         ses = DecodeSession(self, idx, n_new, temperature, top_k, generator.state, eos, return_logits, top_p=top_p,
-                            prompt_lens=lens, pad_token_id=pad, processors=procs)
+                            prompt_lens=lens, pad_token_id=pad, processors=procs, history=hist)
         if _after_prefill is not None:
             _after_prefill(ses.cache)
         if n_new > 1 and use_graph:
@@ -458,22 +472,37 @@ class GPT(tnn.Module):
 class _CpuProcSampler:
     """The sampling step of the CPU generations when logit processors are on: ``ops.sample`` on a CPU
     ``DecodeState`` and ``TokenCounts``, the path the GPU takes, so that eos, the step that ``min_new_tokens``
-    compares with and the counts are kept in one place.  Advances ``generator`` by one draw per call."""
+    compares with and the counts are kept in one place.  Advances ``generator`` by one draw per call.
 
-    def __init__(self, procs, idx, lens, V, generator, temperature, top_k, eos, top_p):
-        self.B, self.V, self.procs, self.generator = idx.shape[0], V, procs, generator
+    With history constraints (``hist``) it also keeps what they read: an output buffer that holds the prompts and
+    receives the tokens, the rows' offsets in the state, and ``stop_hit``."""
+
+    def __init__(self, procs, idx, lens, V, generator, temperature, top_k, eos, top_p, hist=None, n_new=0):
+        self.B, self.V, self.generator = idx.shape[0], V, generator
+        self.procs = D.LogitProcessors(eos_token_id=eos) if procs is None else procs
         self.args = (temperature, top_k, eos)
         self.top_p = top_p
         self.state = D.DecodeState("cpu", generator.state)
         self.counts = None
         self.prompt = (idx, lens)
+        self.hist, self.kw, self.stop_hit = hist, {}, None
+        if hist is not None:
+            T0 = idx.shape[1] if lens is None else max(lens)
+            self.state.reset(generator.state, row_offsets=None if lens is None else [n - T0 for n in lens])
+            out = torch.zeros(self.B, T0 + n_new, dtype=torch.int64)
+            out[:, :T0] = idx[:, :T0]                 # columns >= len_b are overwritten before they are history
+            if hist.stop_sequences:
+                self.stop_hit = torch.full((self.B,), -1, dtype=torch.int32)
+            self.kw = dict(history=hist, out=out, T0=T0, stop_hit=self.stop_hit)
 
     def __call__(self, logits):
         if self.counts is None:          # the logits' width is the counts' width
             self.counts = D.TokenCounts(self.B, logits.shape[1]).add_prompt(*self.prompt)
             self.bias = self.procs.bias(self.B, self.V, logits.shape[1])
+            if self.hist is not None:
+                self.bias = self.hist.merge_bias(self.bias, self.V, logits.shape[1])
         tok = D.sample(logits, self.V, self.state, *self.args, top_p=self.top_p, processors=self.procs,
-                       counts=self.counts, _bias=self.bias).clone()
+                       counts=self.counts, _bias=self.bias, **self.kw).clone()
         self.generator.state.copy_(self.state.rng)
         return tok
 
@@ -492,12 +521,19 @@ class DecodeSession:
     when any of them is on, the session allocates the token counts, the sampler's workspace and the padded
     bias once, sets the prompt flags before the prefill's sample, and every sample passes them; the counts
     live on the device and the sampler advances them, so a replayed step sees the history.  When none is on,
-    ``counts``, ``work`` and ``bias`` stay ``None`` and the sampler is called exactly as without them."""
+    ``counts``, ``work`` and ``bias`` stay ``None`` and the sampler is called exactly as without them.
+
+    The history constraints (``history``, an ``ops.HistoryConstraints``, or the three keywords of ``GPT.generate``)
+    read the rows' histories from ``out``.  When any is on, the session allocates what the processors need (they
+    share the kernel's prologue), with stop sequences also ``stop_hit`` (int32 ``[B]`` on the device: ``-1``, or
+    the index of the stop sequence that finished the row), and passes ``history`` on every sample, the prefill's
+    included.  When none is on, ``history`` and ``stop_hit`` stay ``None``."""
 
     def __init__(self, model, idx, n_new, temperature=1.0, top_k=None, rng_state=None, eos=None,
                  return_logits=False, top_p=None, prompt_lens=None, pad_token_id=0, processors=None,
                  repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None,
-                 suppress_tokens=None, min_new_tokens=0):
+                 suppress_tokens=None, min_new_tokens=0, history=None, no_repeat_ngram_size=0, bad_words_ids=None,
+                 stop_sequences=None):
         cfg, t = model.config, model.transformer
         dev = idx.device
         B, Tin = idx.shape
@@ -507,8 +543,14 @@ class DecodeSession:
                                            suppress_tokens, min_new_tokens, eos)
         processors.check(B, cfg.vocab_size, dev)
         # inactive processors: no counts, no workspace, and _sample calls exactly what it called without them
-        self.processors = processors if processors.active else None
-        self.counts = self.work = self.bias = None
+        if history is None:
+            history = D.HistoryConstraints(no_repeat_ngram_size, bad_words_ids, stop_sequences, eos)
+        history.check(cfg.vocab_size)
+        if history.stop_sequences and history.eos_token_id != eos:
+            raise ValueError("generate: the stop sequences' eos_token_id differs from eos")
+        self.history = history if history.active else None
+        self.processors = processors if processors.active or self.history is not None else None
+        self.counts = self.work = self.bias = self.stop_hit = None
         if prompt_lens is None:
             lens = None
             T0 = Tin
@@ -569,6 +611,10 @@ class DecodeSession:
             self.counts = D.TokenCounts(B, Vp, dev).add_prompt(idx, self.state, T0=T0)
             self.work = torch.empty(B, Vp, device=dev, dtype=torch.bfloat16)
             self.bias = self.processors.bias(B, self.V, Vp, dev)
+            if self.history is not None:
+                self.bias = self.history.merge_bias(self.bias, self.V, Vp, dev)
+                if self.history.stop_sequences:
+                    self.stop_hit = torch.full((B,), -1, device=dev, dtype=torch.int32)
         self._sample(D.skinny_linear(h, wte))      # token T0; the state now points at it
 
     def _sample(self, logits):
@@ -576,7 +622,8 @@ class DecodeSession:
         if self.processors is not None:
             D.sample(logits, self.V, self.state, temperature, top_k, eos, next=self.next, out=self.out,
                      logits_out=self.logits_out, T0=self.T0, top_p=top_p, processors=self.processors,
-                     counts=self.counts, processed_out=self.work, _bias=self.bias)
+                     counts=self.counts, processed_out=self.work, _bias=self.bias, history=self.history,
+                     stop_hit=self.stop_hit)
             return
         D.sample(logits, self.V, self.state, temperature, top_k, eos, next=self.next, out=self.out,
                  logits_out=self.logits_out, T0=self.T0, top_p=top_p)
@@ -597,6 +644,7 @@ class DecodeSession:
         dev = self.next.device
         saved = (self.state.buf.clone(), self.next.clone())
         counts = None if self.counts is None else self.counts.buf.clone()    # the warm-up step counts its token
+        stop_hit = None if self.stop_hit is None else self.stop_hit.clone()  # ... and may stop a row
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(dev)
         side.wait_stream(cur)
@@ -607,6 +655,8 @@ class DecodeSession:
         self.next.copy_(saved[1])
         if counts is not None:
             self.counts.buf.copy_(counts)
+        if stop_hit is not None:
+            self.stop_hit.copy_(stop_hit)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             self.step()

@@ -51,6 +51,30 @@ step 3 is skipped without a bias (``suppress_tokens`` are a bias of ``-inf``).  
 then applies to ``y``, unchanged.  ``return_logits`` / ``logits_out`` keep returning the raw model logits.  A
 row whose every token is banned is the caller's error: it yields some token ``< V``.
 
+History constraints (``HistoryConstraints``; ``sample(..., history=)`` on the GPU, ``history_bans_reference`` and the
+stop rule of ``sample`` on the CPU).  For row ``b`` at generation step ``s``, ``len_b`` its prompt length,
+``L = len_b + s`` and ``h[0 .. L-1] = out[b, 0 : L]`` -- the prompt, then what the row generated, eos forced on
+a finished row included:
+
+1. No-repeat n-gram, ``no_repeat_ngram_size = n >= 1`` (0: off).  If ``L >= n - 1``, let
+   ``P = h[L-n+1 .. L-1]`` (``n - 1`` tokens, empty for ``n = 1``).  Token ``v`` is banned iff some ``j`` with
+   ``n-1 <= j <= L-1`` has ``h[j-n+1 .. j-1] == P`` and ``h[j] == v``.  The prompt counts, as in Hugging Face's
+   ``NoRepeatNGramLogitsProcessor``, and so does ``j = L-1``: the matched window may overlap ``P`` itself (with
+   ``n = 2``, a history ``.. a a`` bans ``a``).  ``n = 1`` bans every token of the history.
+2. Banned sequences, ``bad_words_ids``: token lists of length ``m >= 1``.  ``m == 1`` is merged into the bias as
+   ``-inf`` on the host, as ``suppress_tokens`` are.  For ``m > 1``: if ``L >= m-1`` and
+   ``h[L-m+1 .. L-1] == seq[:m-1]``, then ``seq[m-1]`` is banned.
+3. A ban sets ``x = -inf`` between steps 3 (bias) and 4 (``min_new_tokens``) of the processors above; steps 5 and
+   the sampling are unchanged, ``return_logits`` stays raw.  A finished row ignores bans: it emits eos.  History
+   tokens outside ``[0, V)`` ban nothing.  A row with every token banned is the caller's error, as above.
+4. Stop sequences, ``stop_sequences``: token lists of length ``m >= 1``; they need ``eos_token_id``.  A row that
+   was not finished emits ``tok`` at step ``s``; if ``s + 1 >= m`` and ``out[b, len_b+s-m+1 .. len_b+s] == seq``
+   with ``tok`` in place, the row becomes finished.  The match lies entirely in the generated tokens: a stop
+   sequence that begins in the prompt does not fire.  The sequence stays in ``out``; from the next step on the
+   row emits ``eos_token_id``, exactly as after an emitted eos.  ``min_new_tokens`` concerns eos only and does
+   not delay a stop.  ``stop_hit[b]`` (int32) is ``-1``, or the lowest index in list order of a sequence that
+   matched when the row finished.
+
 GPU tensors always run the framework kernels; an unsupported shape raises ``NotImplementedError``.
 """
 from __future__ import annotations
@@ -548,9 +572,140 @@ def process_logits_reference(logits, V: int, counts, processors: LogitProcessors
     return y
 
 
+# --------------------------------------------------------------------------------------- history constraints
+def _token_lists(seqs, name, max_len, max_seqs):
+    if seqs is None:
+        return []
+    if torch.is_tensor(seqs):
+        seqs = seqs.tolist()
+    res = []
+    for seq in seqs:
+        seq = seq.tolist() if torch.is_tensor(seq) else seq
+        if not isinstance(seq, (list, tuple)) or len(seq) == 0:
+            raise ValueError(f"HistoryConstraints: {name} must be non-empty lists of token ids (got {seq!r})")
+        if len(seq) > max_len:
+            raise ValueError(f"HistoryConstraints: a sequence of {name} holds at most {max_len} tokens "
+                             f"(got {len(seq)})")
+        for t in seq:
+            if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 0 or t >= 1 << 31:
+                raise ValueError(f"HistoryConstraints: {name} must hold token ids >= 0 (got {t!r})")
+        res.append([int(t) for t in seq])
+    if len(res) > max_seqs:
+        raise ValueError(f"HistoryConstraints: at most {max_seqs} sequences in {name} (got {len(res)})")
+    return res
+
+
+def _pack_table(seqs):
+    """``[count + 1 offsets][tokens]`` int32 (PdeSampleHist in ``pde_decode.h``)"""
+    offs = [0]
+    for seq in seqs:
+        offs.append(offs[-1] + len(seq))
+    return torch.tensor(offs + [t for seq in seqs for t in seq], dtype=torch.int32)
+
+
+class HistoryConstraints:
+    """No-repeat n-gram, banned sequences and stop sequences of a generation, validated on the host
+    (``ValueError``: non-integers, negative ids, empty sequences, stop sequences without ``eos_token_id``, limits
+    exceeded; ids ``>= V`` in ``check``).  The definition is in the module docstring.
+
+    Limits: ``no_repeat_ngram_size <= 8``; a sequence holds at most 16 tokens; ``bad_words_ids`` holds at most 256
+    sequences of two or more tokens (single tokens are merged into the bias and not limited), ``stop_sequences``
+    at most 256.  ``active`` is False when nothing is set: the sampler then runs as without constraints."""
+
+    MAX_NGRAM, MAX_SEQ_LEN, MAX_SEQS = 8, 16, 256
+
+    def __init__(self, no_repeat_ngram_size: int = 0, bad_words_ids=None, stop_sequences=None, eos_token_id=None):
+        n = no_repeat_ngram_size
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= self.MAX_NGRAM:
+            raise ValueError(f"HistoryConstraints: no_repeat_ngram_size must be an integer in 0 .. {self.MAX_NGRAM} "
+                             f"(got {n!r})")
+        self.no_repeat_ngram_size = int(n)
+        bad = _token_lists(bad_words_ids, "bad_words_ids", self.MAX_SEQ_LEN, 1 << 30)
+        self.bad_tokens = sorted({seq[0] for seq in bad if len(seq) == 1})      # merged into the bias
+        self.bad_words = [seq for seq in bad if len(seq) > 1]
+        if len(self.bad_words) > self.MAX_SEQS:
+            raise ValueError(f"HistoryConstraints: at most {self.MAX_SEQS} sequences of two or more tokens in "
+                             f"bad_words_ids (got {len(self.bad_words)})")
+        self.stop_sequences = _token_lists(stop_sequences, "stop_sequences", self.MAX_SEQ_LEN, self.MAX_SEQS)
+        e = eos_token_id
+        if e is not None and (isinstance(e, bool) or not isinstance(e, (int, np.integer)) or e < 0):
+            raise ValueError(f"HistoryConstraints: eos_token_id must be a token id >= 0 (got {e!r})")
+        self.eos_token_id = None if e is None else int(e)
+        if self.stop_sequences and self.eos_token_id is None:
+            raise ValueError("HistoryConstraints: stop_sequences need eos_token_id")
+        self._tables, self._checked = {}, set()
+
+    @property
+    def active(self) -> bool:
+        return (self.no_repeat_ngram_size > 0 or bool(self.bad_words) or bool(self.bad_tokens)
+                or bool(self.stop_sequences))
+
+    def check(self, V: int):
+        """The check that needs the vocabulary: token ids ``< V``."""
+        if V in self._checked:
+            return self
+        for name, seqs in (("bad_words_ids", self.bad_words + [self.bad_tokens]),
+                           ("stop_sequences", self.stop_sequences)):
+            if any(t >= V for seq in seqs for t in seq):
+                raise ValueError(f"HistoryConstraints: {name} outside [0, {V})")
+        if self.eos_token_id is not None and self.eos_token_id >= V:
+            raise ValueError(f"HistoryConstraints: eos_token_id outside [0, {V}) (got {self.eos_token_id})")
+        self._checked.add(V)
+        return self
+
+    def tables(self, device=None):
+        """``(banned, stop)``: the packed int32 sequence tables on ``device`` (``None`` for an empty one), made
+        once per device."""
+        dev = torch.device("cpu" if device is None else device)
+        if dev not in self._tables:
+            self._tables[dev] = tuple(_pack_table(s).to(dev) if s else None
+                                      for s in (self.bad_words, self.stop_sequences))
+        return self._tables[dev]
+
+    def merge_bias(self, bias, V: int, Vp=None, device=None):
+        """``bias`` (the processors' padded fp32 ``[1 or B, Vp]``, or ``None``) with ``-inf`` at the single-token
+        ``bad_words_ids``: a new tensor, or ``bias`` itself without any."""
+        if not self.bad_tokens:
+            return bias
+        self.check(V)
+        if bias is None:
+            bias = torch.zeros(1, V if Vp is None else int(Vp), dtype=torch.float32,
+                               device=torch.device("cpu" if device is None else device))
+        else:
+            bias = bias.clone()
+        bias[:, torch.tensor(self.bad_tokens, dtype=torch.int64, device=bias.device)] = -math.inf
+        return bias
+
+
+def history_bans_reference(out, lengths, V: int, history: HistoryConstraints):
+    """Rules 1 and 2 of the history constraints (module docstring) in numpy: ``out`` is ``[B, >= max L]`` int64,
+    ``lengths`` the ``B`` history lengths ``L = len_b + step``.  Returns bool ``[B, V]``: token ``v`` of row ``b`` is
+    banned.  Single-token ``bad_words_ids`` are not here: they are part of the bias."""
+    hs = out.detach().cpu().numpy()
+    B = hs.shape[0]
+    n = history.no_repeat_ngram_size
+    ban = np.zeros((B, V), dtype=bool)
+    for b in range(B):
+        L = int(lengths[b])
+        if not 0 <= L <= hs.shape[1]:
+            raise ValueError(f"history_bans_reference: row {b} has length {L}, out holds {hs.shape[1]} columns")
+        h = hs[b, :L]
+        if n >= 1 and L >= n - 1:
+            P = h[L - n + 1:L]
+            for j in range(n - 1, L):
+                if np.array_equal(h[j - n + 1:j], P) and 0 <= h[j] < V:
+                    ban[b, h[j]] = True
+        for seq in history.bad_words:
+            m = len(seq)
+            if L >= m - 1 and np.array_equal(h[L - m + 1:L], np.asarray(seq[:-1], dtype=hs.dtype)) and seq[-1] < V:
+                ban[b, seq[-1]] = True
+    return torch.from_numpy(ban)
+
+
 def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=None, eos_token_id=None,
            next=None, out=None, logits_out=None, T0: int = 0, threshold_out=None, top_p=None,
-           processors=None, counts=None, processed_out=None, _force_proc=False, _bias=None):
+           processors=None, counts=None, processed_out=None, _force_proc=False, _bias=None, history=None,
+           stop_hit=None):
     """Sample one token per row of the ``[B, Vp]`` bf16 logits on the device (one block per row).
 
     With a ``DecodeState`` the launch also does the bookkeeping of a generation step: the token goes to
@@ -569,14 +724,37 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
     written.  ``logits_out`` receives the raw logits all the same.  Processors whose ``active`` is False run the
     sampler exactly as without them.  Their ``eos_token_id`` stands in for a missing ``eos_token_id`` here.
     CPU tensors run ``process_logits_reference`` and ``sample_reference`` (with the same bookkeeping on a
-    ``DecodeState``)."""
+    ``DecodeState``).
+
+    ``history`` (a ``HistoryConstraints``) applies the history constraints of the module docstring.  The history
+    of row ``b`` is ``out[b, : T0 + off_b + step]``, so ``out`` is needed and holds the prompts; stop sequences
+    need ``stop_hit`` (int32 ``[B]`` on the logits' device, ``-1`` in rows that have not stopped) and an eos.  The
+    constraints run on top of the processors' kernel: without ``processors`` neutral ones are used, and without
+    ``counts`` a scratch one.  Constraints whose ``active`` is False change nothing.  CPU tensors run
+    ``history_bans_reference`` and the stop rule with the same bookkeeping."""
     if temperature < 0:
         raise ValueError("temperature must be >= 0")
     if top_k is not None and top_k < 1:
         raise ValueError("top_k must be >= 1")
     nucleus = check_top_p(top_p, "sample")
     B = logits.shape[0]
-    proc = processors is not None and (processors.active or bool(_force_proc))
+    hist = history is not None and history.active
+    if hist:
+        history.check(V)
+        if out is None or out.dim() != 2 or out.shape[0] != B or out.dtype != torch.int64 or not out.is_contiguous():
+            raise ValueError("sample: history constraints read the rows' histories from `out`, contiguous int64 [B, .]")
+        if eos_token_id is None:
+            eos_token_id = history.eos_token_id
+        elif history.stop_sequences and int(eos_token_id) != history.eos_token_id:
+            raise ValueError("sample: eos_token_id differs from the constraints' eos_token_id")
+        if history.stop_sequences and (stop_hit is None or tuple(stop_hit.shape) != (B,)
+                                       or stop_hit.dtype != torch.int32 or stop_hit.device != logits.device):
+            raise ValueError("sample: stop sequences need `stop_hit`, int32 [B] on the logits' device")
+        if processors is None:
+            processors = LogitProcessors(eos_token_id=eos_token_id)
+        if counts is None and not processors.active:
+            counts = TokenCounts(B, logits.shape[1], logits.device)        # neutral processors read nothing from it
+    proc = hist or (processors is not None and (processors.active or bool(_force_proc)))
     if proc:
         if not isinstance(counts, TokenCounts) or tuple(counts.buf.shape) != tuple(logits.shape) \
                 or counts.buf.device != logits.device:
@@ -585,7 +763,11 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
             eos_token_id = processors.eos_token_id
         elif processors.min_new_tokens > 0 and int(eos_token_id) != processors.eos_token_id:
             raise ValueError("sample: eos_token_id differs from the processors' eos_token_id")
-        bias = processors.bias(B, V, logits.shape[1], logits.device) if _bias is None else _bias
+        bias = _bias
+        if bias is None:
+            bias = processors.bias(B, V, logits.shape[1], logits.device)
+            if hist:
+                bias = history.merge_bias(bias, V, logits.shape[1], logits.device)
         if processed_out is not None and (tuple(processed_out.shape) != tuple(logits.shape)
                                           or processed_out.dtype != logits.dtype
                                           or processed_out.device != logits.device):
@@ -602,17 +784,32 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
     if not logits.is_cuda:
         step = state.step()
         y = logits
+        offs = state.row_offsets[:B].tolist() + [0] * max(B - MAX_ROWS, 0)
+        was_fin = state.finished[:B].bool() if eos >= 0 else torch.zeros(B, dtype=torch.bool)
         if proc:
             y = process_logits_reference(logits, V, counts, processors, step, _bias=bias)
+            if hist:                     # a finished row ignores bans: it emits eos
+                ban = history_bans_reference(out, [T0 + off + step for off in offs], V, history)
+                y[:, :V][ban & ~was_fin[:, None]] = -math.inf
             if processed_out is not None:
                 processed_out.copy_(y)
         tok = sample_reference(y, V, state, temperature, top_k, top_p=top_p)
         if eos >= 0:
-            fin = state.finished[:B].bool()
+            fin = was_fin
             tok = torch.where(fin, torch.full_like(tok, eos), tok)
             state.finished[:B] = (fin | (tok == eos)).int()
+        if hist and history.stop_sequences:
+            for b, off in enumerate(offs):
+                if was_fin[b]:
+                    continue
+                gen = out[b, T0 + off:T0 + off + step].tolist() + [int(tok[b])]
+                for q, seq in enumerate(history.stop_sequences):
+                    if len(gen) >= len(seq) and gen[len(gen) - len(seq):] == seq:
+                        state.finished[b] = 1
+                        stop_hit[b] = q
+                        break
         next.copy_(tok)
-        for b, off in enumerate(state.row_offsets[:B].tolist() + [0] * max(B - MAX_ROWS, 0)):
+        for b, off in enumerate(offs):
             if 0 <= T0 + off + step < out.shape[1]:
                 out[b, T0 + off + step] = tok[b]
         if logits_out is not None and step < logits_out.shape[1]:
@@ -627,6 +824,17 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
         raise NotImplementedError(f"sample: at most {MAX_ROWS} rows on the GPU (got {B})")
     greedy = temperature == 0
     inv_temp = 0.0 if greedy else float(np.float32(1.0 / temperature))
+    if hist:
+        work = torch.empty_like(logits) if processed_out is None else processed_out
+        ban, stop = history.tables(logits.device)
+        kernels().decode_sample_hist(logits, int(V), state.buf, next, out, logits_out, int(T0), inv_temp, greedy,
+                                     0 if top_k is None else int(top_k), eos, threshold_out,
+                                     float(top_p) if nucleus else 0.0, counts.buf, bias, work,
+                                     float(processors.rep), float(processors.inv_rep), float(processors.freq),
+                                     float(processors.pres), processors.min_new_tokens,
+                                     history.no_repeat_ngram_size, ban, len(history.bad_words), stop,
+                                     len(history.stop_sequences), stop_hit if history.stop_sequences else None)
+        return next
     if proc:
         work = torch.empty_like(logits) if processed_out is None else processed_out
         kernels().decode_sample_proc(logits, int(V), state.buf, next, out, logits_out, int(T0), inv_temp, greedy,

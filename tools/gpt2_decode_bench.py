@@ -22,9 +22,13 @@ the logits of the prefill: N back-to-back calls between one event pair, with the
 top-p off.  ``--penalties`` adds a second row per batch size, from the same process and prompt: the same step
 with the logit processors on (``repetition_penalty`` 1.3, ``frequency_penalty`` 0.3, ``presence_penalty`` 0.5 and
 a ``[V]`` logit bias), and under ``--sampler-reps`` the sampler launch with them (the ``PROC`` instantiation).
+``--history`` adds a row with the history constraints on (``no_repeat_ngram_size`` 3 and two stop sequences that
+never match, so every row stays live and is scanned at every step; on top of the penalties under ``--penalties``),
+and under ``--sampler-reps`` the sampler launch with them (the ``HIST`` instantiation) on a 512-token history.
 
     python tools/gpt2_decode_bench.py [--context 512] [--window 64] [--rounds 5] [--batch-sizes 1 16]
                                       [--top-k 50] [--top-p P] [--ragged] [--sampler-reps N] [--penalties]
+                                      [--history]
 """
 import argparse
 import json
@@ -60,15 +64,25 @@ def penalty_processors(cfg, dev):
     return D.LogitProcessors(repetition_penalty=1.3, frequency_penalty=0.3, presence_penalty=0.5, logit_bias=bias)
 
 
-def bench_sampler(B, cfg, top_k, top_p, reps, dev, procs=None):
+def history_constraints(cfg):
+    """The constraints of the ``--history`` row; 50256 ends no stop sequence of the random prompt's tokens"""
+    return D.HistoryConstraints(no_repeat_ngram_size=3, stop_sequences=[[198, 198, 50256], [628, 50256]],
+                                eos_token_id=cfg.vocab_size - 2)
+
+
+def bench_sampler(B, cfg, top_k, top_p, reps, dev, procs=None, hist=None, context=512):
     """us per sampler launch (k_sample + tail), ``reps`` calls between one event pair"""
     logits = (torch.randn(B, cfg.padded_vocab, device=dev) * 3).to(torch.bfloat16)
     state = D.DecodeState(dev, DeviceRNG(0, device=dev).state)
     nxt = torch.zeros(B, device=dev, dtype=torch.int64)
     out = torch.zeros(B, 1, device=dev, dtype=torch.int64)
     kw = {}
+    if hist is not None:             # a history of `context` tokens; the step advances, so leave room for the calls
+        out = torch.randint(0, cfg.vocab_size - 2, (B, context + reps + 11), device=dev)
+        procs = D.LogitProcessors(eos_token_id=hist.eos_token_id) if procs is None else procs
+        kw = dict(history=hist, stop_hit=torch.full((B,), -1, device=dev, dtype=torch.int32), T0=context)
     if procs is not None:            # buffers allocated once, as a generation does
-        kw = dict(processors=procs, counts=D.TokenCounts(B, cfg.padded_vocab, dev),
+        kw = dict(kw, processors=procs, counts=D.TokenCounts(B, cfg.padded_vocab, dev),
                   processed_out=torch.empty_like(logits), _bias=procs.bias(B, cfg.vocab_size, cfg.padded_vocab, dev))
     for _ in range(10):
         D.sample(logits, cfg.vocab_size, state, 1.0, top_k, next=nxt, out=out, top_p=top_p, **kw)
@@ -82,9 +96,10 @@ def bench_sampler(B, cfg, top_k, top_p, reps, dev, procs=None):
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
-def bench_decode(model, idx, a, lens=None, procs=None):
+def bench_decode(model, idx, a, lens=None, procs=None, hist=None):
     ses = DecodeSession(model, idx, a.window + 1, 1.0, a.top_k or None, DeviceRNG(0, device=idx.device).state,
-                        top_p=a.top_p, prompt_lens=lens, processors=procs)
+                        eos=None if hist is None else hist.eos_token_id, top_p=a.top_p, prompt_lens=lens,
+                        processors=procs, history=hist)
     graph = ses.capture()
     start = (ses.state.buf.clone(), ses.next.clone(), None if ses.counts is None else ses.counts.buf.clone())
 
@@ -93,6 +108,8 @@ def bench_decode(model, idx, a, lens=None, procs=None):
         ses.next.copy_(start[1])
         if start[2] is not None:
             ses.counts.buf.copy_(start[2])
+        if ses.stop_hit is not None:
+            ses.stop_hit.fill_(-1)
 
     per_replay, per_window, eager = [], [], []
     for r in range(a.rounds + 1):                       # round 0 is warm-up
@@ -145,6 +162,7 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="prompt lengths spread from 1 to --context")
     ap.add_argument("--sampler-reps", type=int, default=0, help="also time the sampler launch alone")
     ap.add_argument("--penalties", action="store_true", help="a second row per batch size with the logit processors on")
+    ap.add_argument("--history", action="store_true", help="a further row with the history constraints on")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("gpt2_decode_bench: needs a GPU (no CPU fallback: a CPU time says nothing about the kernels)")
@@ -161,16 +179,21 @@ def main():
             # keys read at positions len .. len + window - 1, summed over the rows
             mean_keys = sum(n + (a.window + 1) / 2.0 for n in (lens or [a.context] * B))
             kv_bytes = cfg.n_layer * 2 * cfg.n_head * mean_keys * 64 * 2
-            for procs in [None] + ([penalty_processors(cfg, dev)] if a.penalties else []):
-                per_replay, per_window, eager = bench_decode(model, idx, a, lens, procs)
-                if procs is None and a.recompute_reps > 0:       # once per batch size, after the plain row
+            pen = penalty_processors(cfg, dev) if a.penalties else None
+            rows = [(None, None)] + ([(pen, None)] if a.penalties else [])
+            rows += [(pen, history_constraints(cfg))] if a.history else []
+            for procs, hist in rows:
+                per_replay, per_window, eager = bench_decode(model, idx, a, lens, procs, hist)
+                if procs is None and hist is None and a.recompute_reps > 0:   # once per batch size, after the plain row
                     rec = bench_recompute(model, idx, a.recompute_reps)
-                extra ={"top_k": a.top_k, "top_p": a.top_p, "prompt_lens": lens, "penalties": procs is not None}
+                extra = {"top_k": a.top_k, "top_p": a.top_p, "prompt_lens": lens, "penalties": procs is not None,
+                         "history": hist is not None}
                 if a.sampler_reps > 0:
                     k = a.top_k or None
+                    args = (a.sampler_reps, dev, procs, hist, a.context)
                     extra["sampler_us_per_launch"] = {
-                        "this_run": round(bench_sampler(B, cfg, k, a.top_p, a.sampler_reps, dev, procs), 2),
-                        "top_p_off": round(bench_sampler(B, cfg, k, None, a.sampler_reps, dev, procs), 2)}
+                        "this_run": round(bench_sampler(B, cfg, k, a.top_p, *args), 2),
+                        "top_p_off": round(bench_sampler(B, cfg, k, None, *args), 2)}
                 ms = statistics.median(per_replay)
                 bps = (weight_bytes + kv_bytes) / (ms * 1e-3)
                 print(json.dumps({
