@@ -100,7 +100,9 @@ void decode_embed(const at::Tensor& tok, const at::Tensor& wte, const at::Tensor
             "decode_embed");
 }
 
-// the checked arguments shared by the sampler entries
+bool given(const OptT& t) { return t.has_value() && t->defined(); }
+
+// the checked core arguments of the sampler entry
 PdeSample sample_args(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next,
                       const at::Tensor& out, const OptT& logits_out, int64_t T0, double inv_temp, bool greedy,
                       int64_t top_k, int64_t eos, const OptT& thr_out, double top_p) {
@@ -123,7 +125,7 @@ PdeSample sample_args(const at::Tensor& logits, int64_t V, const at::Tensor& sta
   a.out = ptr<int64_t>(out);
   a.logits_out = nullptr;
   a.max_new = 0;
-  if (logits_out.has_value() && logits_out->defined()) {
+  if (given(logits_out)) {
     check_cuda(*logits_out, "logits_out", BF16);
     TORCH_CHECK(logits_out->dim() == 3 && logits_out->size(0) == B && logits_out->size(2) == V,
                 "sample: logits_out must be [B, max_new, V]");
@@ -144,15 +146,6 @@ PdeSample sample_args(const at::Tensor& logits, int64_t V, const at::Tensor& sta
   return a;
 }
 
-void sample(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next, const at::Tensor& out,
-            const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k, int64_t eos,
-            const OptT& thr_out, double top_p) {
-  hip_check(pde_sample(sample_args(logits, V, state, next, out, logits_out, T0, inv_temp, greedy, top_k, eos, thr_out,
-                                   top_p),
-                       cur_stream()),
-            "sample");
-}
-
 // The sampler with the logit processors (PdeSampleProc in pde_decode.h).  counts: int32 [B, Vp]; bias: fp32
 // [1 or B, Vp] or None; work: bf16 [B, Vp], receives the processed logits; rep / inv_rep: fp32(r), fp32(1 / r).
 PdeSampleProc proc_args(const PdeSample& a, const at::Tensor& logits, const at::Tensor& counts, const OptT& bias,
@@ -170,7 +163,7 @@ PdeSampleProc proc_args(const PdeSample& a, const at::Tensor& logits, const at::
   p.work = work.data_ptr();
   p.bias = nullptr;
   p.bias_stride = 0;
-  if (bias.has_value() && bias->defined()) {
+  if (given(bias)) {
     check_cuda(*bias, "bias", F32);
     TORCH_CHECK(bias->dim() == 2 && (bias->size(0) == 1 || bias->size(0) == B) && bias->size(1) == Vp,
                 "sample: the padded bias must be [1 or B, Vp]");
@@ -188,38 +181,44 @@ PdeSampleProc proc_args(const PdeSample& a, const at::Tensor& logits, const at::
   return p;
 }
 
-void sample_proc(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next,
-                 const at::Tensor& out, const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k,
-                 int64_t eos, const OptT& thr_out, double top_p, const at::Tensor& counts, const OptT& bias,
-                 const at::Tensor& work, double rep, double inv_rep, double freq, double pres, int64_t min_new) {
-  const PdeSample a = sample_args(logits, V, state, next, out, logits_out, T0, inv_temp, greedy, top_k, eos, thr_out,
-                                  top_p);
-  const PdeSampleProc p = proc_args(a, logits, counts, bias, work, rep, inv_rep, freq, pres, min_new);
-  hip_check(pde_sample_proc(a, p, cur_stream()), "sample");
-}
-
 // a packed sequence table (PdeSampleHist in pde_decode.h): int32 [count + 1 offsets][tokens], or None with count 0
 const int* seq_table(const OptT& t, int64_t count, const char* name) {
   TORCH_CHECK(count >= 0 && count <= PDE_HIST_MAX_SEQS, "sample: ", name, " holds 0 .. ", PDE_HIST_MAX_SEQS,
               " sequences, got ", count);
   if (count == 0) return nullptr;
-  TORCH_CHECK(t.has_value() && t->defined(), "sample: ", name, " is missing");
+  TORCH_CHECK(given(t), "sample: ", name, " is missing");
   check_cuda(*t, name, I32);
   TORCH_CHECK(t->dim() == 1 && t->numel() >= 2 * count + 1, "sample: ", name, " must be [count + 1 offsets][tokens]");
   return ptr<int>(*t);
 }
 
-// The sampler with the history constraints on top of the processors (PdeSampleHist in pde_decode.h).  ban / stop:
-// packed int32 sequence tables or None; stop_hit: int32 [B], needed with stop sequences.
-void sample_hist(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next,
-                 const at::Tensor& out, const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k,
-                 int64_t eos, const OptT& thr_out, double top_p, const at::Tensor& counts, const OptT& bias,
-                 const at::Tensor& work, double rep, double inv_rep, double freq, double pres, int64_t min_new,
-                 int64_t ngram, const OptT& ban, int64_t n_ban, const OptT& stop, int64_t n_stop,
-                 const OptT& stop_hit) {
+// The one sampler entry.  The processor group (counts, bias, work, rep, inv_rep, freq, pres, min_new) is on when counts
+// and work are given and launches pde_sample_proc; the history group (ngram, ban, n_ban, stop, n_stop, stop_hit) is on
+// when any of its arguments is set, needs the processor group (the history kernel sits on the processors' prologue)
+// and launches pde_sample_hist.  ban / stop: packed int32 sequence tables or None; stop_hit: int32 [B], needed with
+// stop sequences.  A group given in part is an error.
+void sample(const at::Tensor& logits, int64_t V, const at::Tensor& state, const at::Tensor& next, const at::Tensor& out,
+            const OptT& logits_out, int64_t T0, double inv_temp, bool greedy, int64_t top_k, int64_t eos,
+            const OptT& thr_out, double top_p, const OptT& counts, const OptT& bias, const OptT& work, double rep,
+            double inv_rep, double freq, double pres, int64_t min_new, int64_t ngram, const OptT& ban, int64_t n_ban,
+            const OptT& stop, int64_t n_stop, const OptT& stop_hit) {
   const PdeSample a = sample_args(logits, V, state, next, out, logits_out, T0, inv_temp, greedy, top_k, eos, thr_out,
                                   top_p);
-  const PdeSampleProc p = proc_args(a, logits, counts, bias, work, rep, inv_rep, freq, pres, min_new);
+  const bool proc = given(counts) && given(work);
+  const bool hist = ngram != 0 || n_ban != 0 || n_stop != 0 || given(ban) || given(stop) || given(stop_hit);
+  TORCH_CHECK(given(counts) == given(work), "sample: the processors take counts and work together");
+  TORCH_CHECK(proc || (!given(bias) && rep == 1.0 && inv_rep == 1.0 && freq == 0.0 && pres == 0.0 && min_new == 0),
+              "sample: processor arguments need counts and work");
+  TORCH_CHECK(proc || !hist, "sample: the history constraints need the processors' counts and work");
+  if (!proc) {
+    hip_check(pde_sample(a, cur_stream()), "sample");
+    return;
+  }
+  const PdeSampleProc p = proc_args(a, logits, *counts, bias, *work, rep, inv_rep, freq, pres, min_new);
+  if (!hist) {
+    hip_check(pde_sample_proc(a, p, cur_stream()), "sample");
+    return;
+  }
   TORCH_CHECK(out.is_contiguous(), "sample: out must be contiguous");
   TORCH_CHECK(ngram >= 0 && ngram <= PDE_HIST_MAX_NGRAM, "sample: no_repeat_ngram_size in 0 .. ", PDE_HIST_MAX_NGRAM,
               ", got ", ngram);
@@ -262,16 +261,11 @@ void register_decode(pybind11::module& m) {
   m.def("decode_embed", &decode_embed);
   m.def("decode_sample", &sample, py::arg("logits"), py::arg("V"), py::arg("state"), py::arg("next"), py::arg("out"),
         py::arg("logits_out"), py::arg("T0"), py::arg("inv_temp"), py::arg("greedy"), py::arg("top_k"), py::arg("eos"),
-        py::arg("thr_out") = py::none(), py::arg("top_p") = 0.0);
-  m.def("decode_sample_proc", &sample_proc, py::arg("logits"), py::arg("V"), py::arg("state"), py::arg("next"),
-        py::arg("out"), py::arg("logits_out"), py::arg("T0"), py::arg("inv_temp"), py::arg("greedy"), py::arg("top_k"),
-        py::arg("eos"), py::arg("thr_out"), py::arg("top_p"), py::arg("counts"), py::arg("bias"), py::arg("work"),
-        py::arg("rep"), py::arg("inv_rep"), py::arg("freq"), py::arg("pres"), py::arg("min_new"));
-  m.def("decode_sample_hist", &sample_hist, py::arg("logits"), py::arg("V"), py::arg("state"), py::arg("next"),
-        py::arg("out"), py::arg("logits_out"), py::arg("T0"), py::arg("inv_temp"), py::arg("greedy"), py::arg("top_k"),
-        py::arg("eos"), py::arg("thr_out"), py::arg("top_p"), py::arg("counts"), py::arg("bias"), py::arg("work"),
-        py::arg("rep"), py::arg("inv_rep"), py::arg("freq"), py::arg("pres"), py::arg("min_new"), py::arg("ngram"),
-        py::arg("ban"), py::arg("n_ban"), py::arg("stop"), py::arg("n_stop"), py::arg("stop_hit"));
+        py::arg("thr_out") = py::none(), py::arg("top_p") = 0.0, py::kw_only(), py::arg("counts") = py::none(),
+        py::arg("bias") = py::none(), py::arg("work") = py::none(), py::arg("rep") = 1.0, py::arg("inv_rep") = 1.0,
+        py::arg("freq") = 0.0, py::arg("pres") = 0.0, py::arg("min_new") = 0, py::arg("ngram") = 0,
+        py::arg("ban") = py::none(), py::arg("n_ban") = 0, py::arg("stop") = py::none(), py::arg("n_stop") = 0,
+        py::arg("stop_hit") = py::none());
   m.def("decode_count_prompt", &count_prompt);
   m.attr("DECODE_STATE_WORDS") = PDE_DS_WORDS;
 }

@@ -350,16 +350,7 @@ hipError_t pde_decode_embed(const int64_t* tok, const void* wte, const void* wpe
 }
 
 hipError_t pde_sample(PdeSample a, hipStream_t st) {
-  if (a.B < 1 || a.B > PDE_DS_MAX_ROWS || a.V < 1 || a.V > a.Vp || a.Vp % 8 != 0 || a.top_k < 0)
-    return hipErrorInvalidValue;
-  if (!(a.top_p >= 0.0)) return hipErrorInvalidValue;
-  if (!a.greedy && a.top_p > 0.0 && a.top_p < 1.0)
-    hipLaunchKernelGGL(k_sample<true>, dim3(a.B), dim3(SM_NT), 0, st, a);
-  else
-    hipLaunchKernelGGL(k_sample<false>, dim3(a.B), dim3(SM_NT), 0, st, a);
-  PDE_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_dec_advance, dim3(1), dim3(64), 0, st, a.state);
-  return hipGetLastError();
+  return sample_ok(a) ? sample_launch(a, st) : hipErrorInvalidValue;
 }
 
 }  // extern "C"

@@ -30,18 +30,7 @@ __global__ __launch_bounds__(256) void k_count_prompt(const int64_t* __restrict_
 extern "C" {
 
 hipError_t pde_sample_proc(PdeSample a, PdeSampleProc p, hipStream_t st) {
-  if (a.B < 1 || a.B > PDE_DS_MAX_ROWS || a.V < 1 || a.V > a.Vp || a.Vp % 8 != 0 || a.top_k < 0)
-    return hipErrorInvalidValue;
-  if (!(a.top_p >= 0.0)) return hipErrorInvalidValue;
-  if (!p.counts || !p.work || (p.bias && p.bias_stride != 0 && p.bias_stride != a.Vp)) return hipErrorInvalidValue;
-  if (p.min_new < 0 || (p.min_new > 0 && a.eos < 0) || a.eos >= a.V) return hipErrorInvalidValue;
-  if (!a.greedy && a.top_p > 0.0 && a.top_p < 1.0)
-    hipLaunchKernelGGL((k_sample<true, PdeSampleProc>), dim3(a.B), dim3(SM_NT), 0, st, a, p);
-  else
-    hipLaunchKernelGGL((k_sample<false, PdeSampleProc>), dim3(a.B), dim3(SM_NT), 0, st, a, p);
-  PDE_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_dec_advance, dim3(1), dim3(64), 0, st, a.state);
-  return hipGetLastError();
+  return sample_ok(a) && proc_ok(a, p) ? sample_launch(a, st, p) : hipErrorInvalidValue;
 }
 
 hipError_t pde_count_prompt(const int64_t* idx, const int* state, int* counts, int B, int width, int stride, int T0,

@@ -1,4 +1,5 @@
-// The device-side sampler of the GPT-2 decode step: device code shared by two translation units.
+// The device-side sampler of the GPT-2 decode step: device code, and the host-side checks and launch tail, shared by
+// three translation units.
 // decode.hip instantiates the plain sampler (k_sample<TOPP>), decode_proc.hip the one with the logit processors
 // (k_sample<TOPP, PdeSampleProc>), decode_hist.hip the one with the history constraints on top of them
 // (k_sample<TOPP, PdeSampleProc, PdeSampleHist>).  They are compiled apart on purpose: in one unit the extra instantiations
@@ -436,3 +437,32 @@ __global__ void k_dec_advance(int* __restrict__ state) {
   }
 }
 
+// ---------------------------------------------------------------------------------------- host side
+// The argument checks of pde_sample, pde_sample_proc and pde_sample_hist, and the tail of their launch.
+static inline bool sample_ok(const PdeSample& a) {
+  return a.B >= 1 && a.B <= PDE_DS_MAX_ROWS && a.V >= 1 && a.V <= a.Vp && a.Vp % 8 == 0 && a.top_k >= 0 &&
+         a.top_p >= 0.0;      // false for a NaN
+}
+static inline bool proc_ok(const PdeSample& a, const PdeSampleProc& p) {
+  if (!p.counts || !p.work || (p.bias && p.bias_stride != 0 && p.bias_stride != a.Vp)) return false;
+  return p.min_new >= 0 && (p.min_new == 0 || a.eos >= 0) && a.eos < a.V;
+}
+static inline bool hist_ok(const PdeSample& a, const PdeSampleHist& h) {
+  if (!a.out || a.out_stride < 1 || h.n < 0 || h.n > PDE_HIST_MAX_NGRAM) return false;
+  if (h.n_ban < 0 || h.n_ban > PDE_HIST_MAX_SEQS || (h.n_ban > 0 && !h.ban)) return false;
+  if (h.n_stop < 0 || h.n_stop > PDE_HIST_MAX_SEQS) return false;
+  return h.n_stop == 0 || (h.stop && h.stop_hit && a.eos >= 0);
+}
+
+// k_sample<TOPP, Proc...> over the checked arguments -- TOPP only when the nucleus stage has something to do --
+// then the state's advance
+template <typename... Proc>
+hipError_t sample_launch(const PdeSample& a, hipStream_t st, Proc... proc) {
+  if (!a.greedy && a.top_p > 0.0 && a.top_p < 1.0)
+    hipLaunchKernelGGL((k_sample<true, Proc...>), dim3(a.B), dim3(SM_NT), 0, st, a, proc...);
+  else
+    hipLaunchKernelGGL((k_sample<false, Proc...>), dim3(a.B), dim3(SM_NT), 0, st, a, proc...);
+  PDE_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_dec_advance, dim3(1), dim3(64), 0, st, a.state);
+  return hipGetLastError();
+}

@@ -326,37 +326,18 @@ class GPT(tnn.Module):
         cfg = self.config
         if idx.dim() != 2 or idx.shape[1] < 1:
             raise ValueError("generate: idx must be [B, T0] with T0 >= 1")
-        B, T0 = idx.shape
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
             raise ValueError("generate: max_new_tokens must be >= 1")
-        lens = None
-        if prompt_lens is not None:
-            lens = [int(n) for n in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
-            if len(lens) != B:
-                raise ValueError(f"generate: prompt_lens holds {len(lens)} lengths for {B} rows")
-            if min(lens) < 1 or max(lens) > T0:
-                raise ValueError(f"generate: every prompt length must be in 1 .. {T0} (got {lens})")
-        Tlong = T0 if lens is None else max(lens)
-        if Tlong + max_new_tokens > cfg.block_size:
-            raise ValueError(f"generate: T0 + max_new_tokens = {Tlong + max_new_tokens} exceeds block_size "
-                             f"{cfg.block_size} (positions are learned and absolute: no sliding window)")
         if not 0 <= int(pad_token_id) < cfg.vocab_size:
             raise ValueError("generate: pad_token_id must be a token of the vocabulary")
-        if temperature < 0:
-            raise ValueError("generate: temperature must be >= 0")
-        if top_k is not None and top_k < 1:
-            raise ValueError("generate: top_k must be >= 1")
-        D.check_top_p(top_p, "generate")
-        if eos_token_id is not None and not 0 <= eos_token_id < cfg.vocab_size:
-            raise ValueError("generate: eos_token_id must be a token of the vocabulary")
         dev = self.transformer.wte.weight.device
-        procs = D.LogitProcessors(repetition_penalty, frequency_penalty, presence_penalty, logit_bias, suppress_tokens,
-                                  min_new_tokens, eos_token_id).check(B, cfg.vocab_size, dev)
-        procs = procs if procs.active else None          # neutral settings: the calls below are what they were
-        hist = D.HistoryConstraints(no_repeat_ngram_size, bad_words_ids, stop_sequences,
-                                    eos_token_id).check(cfg.vocab_size)
-        hist = hist if hist.active else None
+        config = D.SamplerConfig(
+            temperature, top_k, top_p, eos_token_id,
+            D.LogitProcessors(repetition_penalty, frequency_penalty, presence_penalty, logit_bias, suppress_tokens,
+                              min_new_tokens, eos_token_id),
+            D.HistoryConstraints(no_repeat_ngram_size, bad_words_ids, stop_sequences, eos_token_id),
+            who="generate")
         if generator is None:
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -367,77 +348,36 @@ class GPT(tnn.Module):
         self.eval()
         try:
             with torch.no_grad():
-                run = self._generate_gpu if dev.type == "cuda" else self._generate_cpu
-                return run(idx.to(dev).long(), max_new_tokens, float(temperature), top_k, generator, eos_token_id,
-                           use_graph, return_logits, _after_prefill, top_p, lens, int(pad_token_id), procs, hist)
+                args = (idx.to(dev).long(), max_new_tokens, config, generator, prompt_lens, int(pad_token_id),
+                        return_logits)
+                if dev.type == "cuda":
+                    return self._generate_gpu(*args, use_graph, _after_prefill)
+                return self._generate_cpu(*args)
         finally:
             self.train(was_training)
 
-    def _generate_cpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill,
-                      top_p=None, lens=None, pad=0, procs=None, hist=None):
-        V = self.config.vocab_size
-        if lens is not None:
-            return self._generate_cpu_ragged(idx, n_new, temperature, top_k, generator, eos, return_logits, top_p,
-                                             lens, pad, procs, hist)
-        seq = idx
-        fin = torch.zeros(idx.shape[0], dtype=torch.bool)
-        kept = []
-        sample = None
-        if procs is not None or hist is not None:
-            sample = _CpuProcSampler(procs, idx, None, V, generator, temperature, top_k, eos, top_p, hist, n_new)
-        for _ in range(n_new):
-            logits = self(seq)[:, -1]
-            if sample is not None:
-                tok = sample(logits)
-            else:
-                tok = D.sample_reference(logits, V, generator.next(), temperature, top_k, top_p=top_p)
-                if eos is not None:
-                    tok = torch.where(fin, torch.full_like(tok, eos), tok)
-                    fin = fin | (tok == eos)
-            seq = torch.cat([seq, tok[:, None]], dim=1)
-            if return_logits:
-                kept.append(logits)
-        return (seq, torch.stack(kept, dim=1)) if return_logits else seq
-
-    def _generate_cpu_ragged(self, idx, n_new, temperature, top_k, generator, eos, return_logits, top_p, lens, pad,
-                             procs=None, hist=None):
+    def _generate_cpu(self, idx, n_new, config, generator, lens, pad, return_logits):
         """One right-padded forward per token; row ``b``'s logits are row ``len_b + s - 1`` of it (causal:
         independent of what follows), gathered into ``[B, V]`` for one sampler call per step, so the
-        Philox row index is ``b`` as on the GPU."""
+        Philox row index is ``b`` as on the GPU.  A batch of one prompt length is the ragged one with every
+        ``len_b = T0``; the sampler's CPU twin keeps eos, the output layout and the draw number."""
         V = self.config.vocab_size
         B, T0 = idx.shape
-        Tl = max(lens)
-        ln = torch.tensor(lens, dtype=torch.int64)
+        lens, Tl = _prompt_window(self.config, idx, n_new, lens, config)
+        buf = D.SampleBuffers(config, idx, lens, n_new, V, V, "cpu", generator.state, pad, return_logits,
+                              dtype=self.transformer.wte.weight.dtype)
+        ln = torch.tensor(lens or [T0] * B, dtype=torch.int64)
         rows = torch.arange(B)
-        real = torch.arange(T0)[None, :] < ln[:, None]
-        out = torch.full((B, T0 + n_new), pad, dtype=torch.int64)
-        out[:, :T0] = torch.where(real, idx, out[:, :T0])
         seq = torch.zeros(B, Tl + n_new, dtype=torch.int64)        # what the model sees: pad columns hold token 0
-        seq[:, :Tl] = torch.where(real[:, :Tl], idx[:, :Tl], seq[:, :Tl])
-        fin = torch.zeros(B, dtype=torch.bool)
-        kept = []
-        sample = None
-        if procs is not None or hist is not None:
-            sample = _CpuProcSampler(procs, idx, lens, V, generator, temperature, top_k, eos, top_p, hist, n_new)
+        seq[:, :Tl] = torch.where(torch.arange(Tl)[None, :] < ln[:, None], idx[:, :Tl], seq[:, :Tl])
         for s in range(n_new):
-            logits = self(seq[:, :Tl + s])[rows, ln + s - 1]
-            if sample is not None:
-                tok = sample(logits)
-            else:
-                tok = D.sample_reference(logits, V, generator.next(), temperature, top_k, top_p=top_p)
-                if eos is not None:
-                    tok = torch.where(fin, torch.full_like(tok, eos), tok)
-                    fin = fin | (tok == eos)
-            seq[rows, ln + s] = tok
-            out[rows, ln + s] = tok
-            if return_logits:
-                kept.append(logits)
-        return (out, torch.stack(kept, dim=1)) if return_logits else out
+            seq[rows, ln + s] = buf.sample(self(seq[:, :Tl + s])[rows, ln + s - 1])
+        generator.state.copy_(buf.state.rng)       # the draw number advanced by n_new
+        return (buf.out, buf.logits_out) if return_logits else buf.out
 
-    def _generate_gpu(self, idx, n_new, temperature, top_k, generator, eos, use_graph, return_logits, _after_prefill,
-                      top_p=None, lens=None, pad=0, procs=None, hist=None):
-        ses = DecodeSession(self, idx, n_new, temperature, top_k, generator.state, eos, return_logits, top_p=top_p,
-                            prompt_lens=lens, pad_token_id=pad, processors=procs, history=hist)
+    def _generate_gpu(self, idx, n_new, config, generator, lens, pad, return_logits, use_graph, _after_prefill):
+        ses = DecodeSession(self, idx, n_new, rng_state=generator.state, return_logits=return_logits, prompt_lens=lens,
+                            pad_token_id=pad, config=config)
         if _after_prefill is not None:
             _after_prefill(ses.cache)
         if n_new > 1 and use_graph:
@@ -469,42 +409,24 @@ class GPT(tnn.Module):
         return 6 * N + 6 * c.n_layer * c.n_embd * c.block_size  # causal: half of 12*L*C*T
 
 
-class _CpuProcSampler:
-    """The sampling step of the CPU generations when logit processors are on: ``ops.sample`` on a CPU
-    ``DecodeState`` and ``TokenCounts``, the path the GPU takes, so that eos, the step that ``min_new_tokens``
-    compares with and the counts are kept in one place.  Advances ``generator`` by one draw per call.
-
-    With history constraints (``hist``) it also keeps what they read: an output buffer that holds the prompts and
-    receives the tokens, the rows' offsets in the state, and ``stop_hit``."""
-
-    def __init__(self, procs, idx, lens, V, generator, temperature, top_k, eos, top_p, hist=None, n_new=0):
-        self.B, self.V, self.generator = idx.shape[0], V, generator
-        self.procs = D.LogitProcessors(eos_token_id=eos) if procs is None else procs
-        self.args = (temperature, top_k, eos)
-        self.top_p = top_p
-        self.state = D.DecodeState("cpu", generator.state)
-        self.counts = None
-        self.prompt = (idx, lens)
-        self.hist, self.kw, self.stop_hit = hist, {}, None
-        if hist is not None:
-            T0 = idx.shape[1] if lens is None else max(lens)
-            self.state.reset(generator.state, row_offsets=None if lens is None else [n - T0 for n in lens])
-            out = torch.zeros(self.B, T0 + n_new, dtype=torch.int64)
-            out[:, :T0] = idx[:, :T0]                 # columns >= len_b are overwritten before they are history
-            if hist.stop_sequences:
-                self.stop_hit = torch.full((self.B,), -1, dtype=torch.int32)
-            self.kw = dict(history=hist, out=out, T0=T0, stop_hit=self.stop_hit)
-
-    def __call__(self, logits):
-        if self.counts is None:          # the logits' width is the counts' width
-            self.counts = D.TokenCounts(self.B, logits.shape[1]).add_prompt(*self.prompt)
-            self.bias = self.procs.bias(self.B, self.V, logits.shape[1])
-            if self.hist is not None:
-                self.bias = self.hist.merge_bias(self.bias, self.V, logits.shape[1])
-        tok = D.sample(logits, self.V, self.state, *self.args, top_p=self.top_p, processors=self.procs,
-                       counts=self.counts, _bias=self.bias, **self.kw).clone()
-        self.generator.state.copy_(self.state.rng)
-        return tok
+def _prompt_window(cfg, idx, n_new, prompt_lens, config):
+    """``(lens, T0)`` of a generation of ``n_new`` tokens after ``idx``: the prompt lengths as a list (``None`` for a
+    batch of one length) and the longest of them, checked against the width of ``idx`` and ``block_size``; and the
+    checks of ``config`` (the ``ops.SamplerConfig``) against the batch, the vocabulary and the device."""
+    B, Tin = idx.shape
+    config.check(B, cfg.vocab_size, idx.device)
+    lens = None
+    if prompt_lens is not None:
+        lens = D._int_list(prompt_lens)
+        if len(lens) != B:
+            raise ValueError(f"generate: prompt_lens holds {len(lens)} lengths for {B} rows")
+        if min(lens) < 1 or max(lens) > Tin:
+            raise ValueError(f"generate: every prompt length must be in 1 .. {Tin} (got {lens})")
+    T0 = Tin if lens is None else max(lens)       # the longest prompt: window, cache length and base position
+    if T0 + n_new > cfg.block_size:
+        raise ValueError(f"generate: T0 + max_new_tokens = {T0 + n_new} exceeds block_size "
+                         f"{cfg.block_size} (positions are learned and absolute: no sliding window)")
+    return lens, T0
 
 
 class DecodeSession:
@@ -527,40 +449,27 @@ class DecodeSession:
     read the rows' histories from ``out``.  When any is on, the session allocates what the processors need (they
     share the kernel's prologue), with stop sequences also ``stop_hit`` (int32 ``[B]`` on the device: ``-1``, or
     the index of the stop sequence that finished the row), and passes ``history`` on every sample, the prefill's
-    included.  When none is on, ``history`` and ``stop_hit`` stay ``None``."""
+    included.  When none is on, ``history`` and ``stop_hit`` stay ``None``.
+
+    ``config`` (an ``ops.SamplerConfig``, as ``GPT.generate`` passes) stands for all the sampling keywords.  The
+    buffers named above live in ``buffers``, an ``ops.SampleBuffers``, and are mirrored as attributes."""
 
     def __init__(self, model, idx, n_new, temperature=1.0, top_k=None, rng_state=None, eos=None,
                  return_logits=False, top_p=None, prompt_lens=None, pad_token_id=0, processors=None,
                  repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None,
                  suppress_tokens=None, min_new_tokens=0, history=None, no_repeat_ngram_size=0, bad_words_ids=None,
-                 stop_sequences=None):
+                 stop_sequences=None, config=None):
         cfg, t = model.config, model.transformer
         dev = idx.device
-        B, Tin = idx.shape
-        D.check_top_p(top_p, "generate")
-        if processors is None:
-            processors = D.LogitProcessors(repetition_penalty, frequency_penalty, presence_penalty, logit_bias,
-                                           suppress_tokens, min_new_tokens, eos)
-        processors.check(B, cfg.vocab_size, dev)
-        # inactive processors: no counts, no workspace, and _sample calls exactly what it called without them
-        if history is None:
-            history = D.HistoryConstraints(no_repeat_ngram_size, bad_words_ids, stop_sequences, eos)
-        history.check(cfg.vocab_size)
-        if history.stop_sequences and history.eos_token_id != eos:
-            raise ValueError("generate: the stop sequences' eos_token_id differs from eos")
-        self.history = history if history.active else None
-        self.processors = processors if processors.active or self.history is not None else None
-        self.counts = self.work = self.bias = self.stop_hit = None
-        if prompt_lens is None:
-            lens = None
-            T0 = Tin
-        else:
-            lens = [int(n) for n in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
-            if len(lens) != B or min(lens) < 1 or max(lens) > Tin:
-                raise ValueError(f"generate: prompt_lens must hold {B} lengths in 1 .. {Tin} (got {lens})")
-            T0 = max(lens)                       # the longest prompt: window, cache length and base position
-        if T0 + n_new > cfg.block_size:
-            raise ValueError(f"generate: T0 + max_new_tokens = {T0 + n_new} exceeds block_size {cfg.block_size}")
+        B = idx.shape[0]
+        if config is None:
+            if processors is None:
+                processors = D.LogitProcessors(repetition_penalty, frequency_penalty, presence_penalty, logit_bias,
+                                               suppress_tokens, min_new_tokens, eos)
+            if history is None:
+                history = D.HistoryConstraints(no_repeat_ngram_size, bad_words_ids, stop_sequences, eos)
+            config = D.SamplerConfig(temperature, top_k, top_p, eos, processors, history, who="generate")
+        lens, T0 = _prompt_window(cfg, idx, n_new, prompt_lens, config)
         wte, wpe = t.wte.weight, t.wpe.weight
         if B > D.MAX_ROWS:
             raise NotImplementedError(f"generate: at most {D.MAX_ROWS} sequences on the GPU (got {B})")
@@ -571,7 +480,6 @@ class DecodeSession:
             raise NotImplementedError("generate: the prefill needs a window that is a multiple of 128 "
                                       f"(block_size {cfg.block_size} caps it at {Tpad})")
         self.model, self.T0, self.V = model, T0, cfg.vocab_size
-        self.sampling = (float(temperature), top_k, eos, top_p)
         # prefill: the training kernels over the padded prompt (causal: the pad never reaches positions < T0)
         self.cache = D.KVCache(cfg, B, T0 + n_new, dev)
         idx_pad = torch.zeros(B, Tpad, device=dev, dtype=torch.int64)
@@ -579,8 +487,8 @@ class DecodeSession:
             idx_pad[:, :T0] = idx
         else:                                    # columns >= len_b hold token 0, whatever idx holds there
             ln = torch.tensor(lens, device=dev, dtype=torch.int64)
-            real = torch.arange(Tin, device=dev)[None, :] < ln[:, None]
-            idx_pad[:, :T0] = torch.where(real[:, :T0], idx[:, :T0], idx_pad[:, :T0])
+            real = torch.arange(T0, device=dev)[None, :] < ln[:, None]
+            idx_pad[:, :T0] = torch.where(real, idx[:, :T0], idx_pad[:, :T0])
         x, delta = T.embedding(idx_pad, wte, wpe), None
         for l, blk in enumerate(t.h):
             x, delta, qkv = blk.forward_deferred_qkv(x, delta)
@@ -595,38 +503,17 @@ class DecodeSession:
             rows = torch.arange(B, device=dev)
             xl, dl = x[rows, ln - 1].contiguous(), delta[rows, ln - 1].contiguous()
         h = T.add_layer_norm_residual(xl, dl, t.ln_f.weight, t.ln_f.bias, t.ln_f.eps)[1]
-        self.state = D.DecodeState(dev, rng_state, pos=T0 - 1, step=0,
-                                   row_offsets=None if lens is None else [n - T0 for n in lens])
-        if lens is None:
-            self.out = torch.zeros(B, T0 + n_new, device=dev, dtype=torch.int64)
-            self.out[:, :T0] = idx
-        else:
-            self.out = torch.full((B, Tin + n_new), int(pad_token_id), device=dev, dtype=torch.int64)
-            self.out[:, :Tin] = torch.where(real, idx, self.out[:, :Tin])
-        self.next = torch.zeros(B, device=dev, dtype=torch.int64)
-        self.logits_out = (torch.empty(B, n_new, self.V, device=dev, dtype=torch.bfloat16)
-                           if return_logits else None)
-        if self.processors is not None:          # allocated once; the prompt flags before the prefill's sample
-            Vp = wte.shape[0]
-            self.counts = D.TokenCounts(B, Vp, dev).add_prompt(idx, self.state, T0=T0)
-            self.work = torch.empty(B, Vp, device=dev, dtype=torch.bfloat16)
-            self.bias = self.processors.bias(B, self.V, Vp, dev)
-            if self.history is not None:
-                self.bias = self.history.merge_bias(self.bias, self.V, Vp, dev)
-                if self.history.stop_sequences:
-                    self.stop_hit = torch.full((B,), -1, device=dev, dtype=torch.int32)
+        # state, next, out and logits_out; with processors or constraints on also counts (the prompt flags set), work,
+        # bias and stop_hit, which stay None otherwise: the sampler is then called exactly as without them
+        self.buffers = b = D.SampleBuffers(config, idx, lens, n_new, self.V, wte.shape[0], dev, rng_state, pad_token_id,
+                                           return_logits)
+        self.processors, self.history = config.processors, config.history
+        self.state, self.next, self.out, self.logits_out = b.state, b.next, b.out, b.logits_out
+        self.counts, self.work, self.bias, self.stop_hit = b.counts, b.work, b.bias, b.stop_hit
         self._sample(D.skinny_linear(h, wte))      # token T0; the state now points at it
 
     def _sample(self, logits):
-        temperature, top_k, eos, top_p = self.sampling
-        if self.processors is not None:
-            D.sample(logits, self.V, self.state, temperature, top_k, eos, next=self.next, out=self.out,
-                     logits_out=self.logits_out, T0=self.T0, top_p=top_p, processors=self.processors,
-                     counts=self.counts, processed_out=self.work, _bias=self.bias, history=self.history,
-                     stop_hit=self.stop_hit)
-            return
-        D.sample(logits, self.V, self.state, temperature, top_k, eos, next=self.next, out=self.out,
-                 logits_out=self.logits_out, T0=self.T0, top_p=top_p)
+        self.buffers.sample(logits)
 
     def step(self):
         """embedding -> blocks (residual adds deferred into the next LayerNorm) -> ln_f -> LM head -> sampler"""
@@ -642,21 +529,14 @@ class DecodeSession:
         the state it advanced (the cache row and output slot it wrote are written again, identically, by
         the first replay)."""
         dev = self.next.device
-        saved = (self.state.buf.clone(), self.next.clone())
-        counts = None if self.counts is None else self.counts.buf.clone()    # the warm-up step counts its token
-        stop_hit = None if self.stop_hit is None else self.stop_hit.clone()  # ... and may stop a row
+        saved = self.buffers.snapshot()           # the warm-up step advances the state, counts its token, may stop a row
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             self.step()
         cur.wait_stream(side)
-        self.state.buf.copy_(saved[0])
-        self.next.copy_(saved[1])
-        if counts is not None:
-            self.counts.buf.copy_(counts)
-        if stop_hit is not None:
-            self.stop_hit.copy_(stop_hit)
+        self.buffers.restore(saved)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             self.step()

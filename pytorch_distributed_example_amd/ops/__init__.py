@@ -14,9 +14,9 @@ from .transformer import LossTargets, doc_bounds, loss_targets  # noqa: F401
 from . import rng  # noqa: F401
 from .rng import DeviceRNG, dropout_mask, effective_p  # noqa: F401
 from . import decode  # noqa: F401
-from .decode import (DecodeState, HistoryConstraints, KVCache, LogitProcessors, TokenCounts,  # noqa: F401
-                     check_top_p, decode_attention, decode_embed, history_bans_reference, key16_to_float,
-                     process_logits_reference, sample, sample_reference, skinny_linear)
+from .decode import (DecodeState, HistoryConstraints, KVCache, LogitProcessors, SampleBuffers,  # noqa: F401
+                     SamplerConfig, TokenCounts, check_top_p, decode_attention, decode_embed, history_bans_reference,
+                     key16_to_float, process_logits_reference, sample, sample_reference, skinny_linear)
 
 
 def linear(x, weight, bias=None):

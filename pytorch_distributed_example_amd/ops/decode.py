@@ -91,8 +91,13 @@ from . import rng as R
 _BF16 = torch.bfloat16
 
 STATE_WORDS = 40          # pde_decode.h
-_RNG, _POS, _STEP, _FIN, _OFF = 0, 4, 5, 8, 24
+_RNG, _POS, _STEP, _FIN = 0, 4, 5, 8
 MAX_ROWS = 16
+
+
+def _int_list(x):
+    """A list or int tensor as a list of Python ints (a host read for a device tensor)."""
+    return [int(n) for n in (x.tolist() if torch.is_tensor(x) else x)]
 
 
 def check_top_p(top_p, who: str = "sample"):
@@ -105,26 +110,32 @@ def check_top_p(top_p, who: str = "sample"):
 
 
 class DecodeState:
-    """The device-side state of a generation: RNG words, position, step, finished flags and per-row
-    position offsets (int32 x 40)."""
+    """The device-side state of a generation: RNG words, position, step, and one finished flag and one position
+    offset per row (int32: 8 words, ``rows`` flags, ``rows`` offsets).  With the default 16 rows it is the 40-word
+    layout of ``pde_decode.h``, the only one the kernels take; a CPU state may hold more rows."""
 
-    def __init__(self, device=None, rng_state=None, pos: int = 0, step: int = 0, row_offsets=None):
+    def __init__(self, device=None, rng_state=None, pos: int = 0, step: int = 0, row_offsets=None,
+                 rows: int = MAX_ROWS):
         self.device = torch.device("cpu" if device is None else device)
-        self.buf = torch.zeros(STATE_WORDS, dtype=torch.int32, device=self.device)
+        self.rows = int(rows)
+        if self.rows < 1 or (self.rows != MAX_ROWS and self.device.type != "cpu"):
+            raise ValueError(f"DecodeState: {MAX_ROWS} rows on the GPU, any number >= 1 on the CPU (got {rows})")
+        self._off = _FIN + self.rows
+        self.buf = torch.zeros(self._off + self.rows, dtype=torch.int32, device=self.device)
         self.reset(rng_state, pos, step, row_offsets)
 
     def reset(self, rng_state=None, pos: int = 0, step: int = 0, row_offsets=None):
         """Position / step / row offsets from the host, RNG words copied from a ``DeviceRNG`` state or
         snapshot (a device-to-device copy: no host read); the finished flags are cleared.  ``row_offsets``
-        (up to 16 ints ``<= 0``, default all 0) are ``len_b - max(len)`` of a ragged prompt batch: row ``b``
+        (up to ``rows`` ints ``<= 0``, default all 0) are ``len_b - max(len)`` of a ragged prompt batch: row ``b``
         is at position ``pos + row_offsets[b]``."""
-        init = torch.zeros(STATE_WORDS, dtype=torch.int32)
+        init = torch.zeros(self.buf.numel(), dtype=torch.int32)
         init[_POS], init[_STEP] = int(pos), int(step)
         if row_offsets is not None:
-            offs = [int(o) for o in (row_offsets.tolist() if torch.is_tensor(row_offsets) else row_offsets)]
-            if len(offs) > MAX_ROWS or any(o > 0 for o in offs):
-                raise ValueError(f"row_offsets: at most {MAX_ROWS} values <= 0 (got {offs})")
-            init[_OFF:_OFF + len(offs)] = torch.tensor(offs, dtype=torch.int32)
+            offs = _int_list(row_offsets)
+            if len(offs) > self.rows or any(o > 0 for o in offs):
+                raise ValueError(f"row_offsets: at most {self.rows} values <= 0 (got {offs})")
+            init[self._off:self._off + len(offs)] = torch.tensor(offs, dtype=torch.int32)
         self.buf.copy_(init)
         if rng_state is not None:
             if tuple(rng_state.shape) != (4,) or rng_state.dtype != torch.int32:
@@ -138,20 +149,26 @@ class DecodeState:
 
     @property
     def finished(self):
-        return self.buf[_FIN:_FIN + MAX_ROWS]
+        return self.buf[_FIN:_FIN + self.rows]
 
     @property
     def row_offsets(self):
-        return self.buf[_OFF:_OFF + MAX_ROWS]
+        return self.buf[self._off:self._off + self.rows]
 
     def pos(self) -> int:
         """The base position: that of the rows with offset 0 (the longest prompts)."""
         return int(self.buf[_POS].item())
 
-    def row_pos(self, B: int = MAX_ROWS):
-        """The positions of rows ``0 .. B-1`` as a list: base position plus row offset (a host read)."""
-        w = self.buf.cpu()
-        return [int(w[_POS]) + (int(w[_OFF + b]) if b < MAX_ROWS else 0) for b in range(B)]
+    def offsets(self, B: int = None):
+        """The position offsets of rows ``0 .. B-1`` (default: all) as a list (a host read)."""
+        if B is not None and B > self.rows:
+            raise ValueError(f"a batch of {B} rows on a decode state of {self.rows}")
+        return self.row_offsets[:B].tolist()
+
+    def row_pos(self, B: int = None):
+        """The positions of rows ``0 .. B-1`` (default: all) as a list: base position plus row offset (a host read)."""
+        pos = self.pos()
+        return [pos + o for o in self.offsets(B)]
 
     def step(self) -> int:
         return int(self.buf[_STEP].item())
@@ -415,8 +432,7 @@ class TokenCounts:
         if isinstance(state_or_lens, DecodeState):
             state, T0 = state_or_lens, width if T0 is None else int(T0)
         else:
-            lens = [width] * B if state_or_lens is None else [
-                int(n) for n in (state_or_lens.tolist() if torch.is_tensor(state_or_lens) else state_or_lens)]
+            lens = [width] * B if state_or_lens is None else _int_list(state_or_lens)
             if len(lens) != B or min(lens) < 0 or max(lens) > width:
                 raise ValueError(f"add_prompt: {B} lengths in 0 .. {width} (got {lens})")
             T0 = max(lens)
@@ -432,8 +448,7 @@ class TokenCounts:
             kernels().decode_count_prompt(idx if idx.is_contiguous() else idx.contiguous(), state.buf, self.buf, T0)
             return self
         if state is not None:
-            offs = state.row_offsets[:B].tolist() + [0] * max(B - MAX_ROWS, 0)
-            lens = [min(max(T0 + o, 0), width) for o in offs]
+            lens = [min(max(T0 + o, 0), width) for o in state.offsets(B)]
         for b, n in enumerate(lens):
             tok = idx[b, :n].long().cpu()
             tok = tok[(tok >= 0) & (tok < Vp)]
@@ -460,6 +475,19 @@ def _finite(x, name):
     if not math.isfinite(x):
         raise ValueError(f"LogitProcessors: {name} must be finite (got {x})")
     return x
+
+
+def _token_id(t, what, exact=True):
+    """``t`` as a token id, or ``ValueError`` in the name of ``what``.  ``exact`` (the history constraints) takes
+    Python and numpy integers in ``[0, 2^31)`` and no bool; otherwise (the logit processors) whatever equals an
+    integer ``>= 0``."""
+    if exact:
+        ok = not isinstance(t, bool) and isinstance(t, (int, np.integer)) and 0 <= t < 1 << 31
+    else:
+        ok = int(t) == t and t >= 0
+    if not ok:
+        raise ValueError(f"{what} must be token ids >= 0 (got {t!r})")
+    return int(t)
 
 
 class LogitProcessors:
@@ -490,16 +518,13 @@ class LogitProcessors:
         if suppress_tokens is None:
             self.suppress_tokens = []
         else:
-            toks = suppress_tokens.tolist() if torch.is_tensor(suppress_tokens) else list(suppress_tokens)
-            if any(int(t) != t or t < 0 for t in toks):
-                raise ValueError(f"LogitProcessors: suppress_tokens must be token ids >= 0 (got {toks})")
-            self.suppress_tokens = sorted({int(t) for t in toks})
+            toks = suppress_tokens.tolist() if torch.is_tensor(suppress_tokens) else suppress_tokens
+            self.suppress_tokens = sorted({_token_id(t, "LogitProcessors: suppress_tokens", False) for t in toks})
         if int(min_new_tokens) != min_new_tokens or min_new_tokens < 0:
             raise ValueError(f"LogitProcessors: min_new_tokens must be an integer >= 0 (got {min_new_tokens})")
         self.min_new_tokens = int(min_new_tokens)
-        if eos_token_id is not None and (int(eos_token_id) != eos_token_id or eos_token_id < 0):
-            raise ValueError(f"LogitProcessors: eos_token_id must be a token id >= 0 (got {eos_token_id})")
-        self.eos_token_id = None if eos_token_id is None else int(eos_token_id)
+        self.eos_token_id = None if eos_token_id is None else _token_id(eos_token_id, "LogitProcessors: eos_token_id",
+                                                                        False)
         if self.min_new_tokens > 0 and self.eos_token_id is None:
             raise ValueError("LogitProcessors: min_new_tokens > 0 needs eos_token_id")
 
@@ -586,10 +611,7 @@ def _token_lists(seqs, name, max_len, max_seqs):
         if len(seq) > max_len:
             raise ValueError(f"HistoryConstraints: a sequence of {name} holds at most {max_len} tokens "
                              f"(got {len(seq)})")
-        for t in seq:
-            if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 0 or t >= 1 << 31:
-                raise ValueError(f"HistoryConstraints: {name} must hold token ids >= 0 (got {t!r})")
-        res.append([int(t) for t in seq])
+        res.append([_token_id(t, f"HistoryConstraints: {name}") for t in seq])
     if len(res) > max_seqs:
         raise ValueError(f"HistoryConstraints: at most {max_seqs} sequences in {name} (got {len(res)})")
     return res
@@ -702,10 +724,119 @@ def history_bans_reference(out, lengths, V: int, history: HistoryConstraints):
     return torch.from_numpy(ban)
 
 
+class SamplerConfig:
+    """The sampling settings of a generation -- ``temperature``, ``top_k``, ``top_p``, ``eos_token_id``, ``processors``
+    (a ``LogitProcessors``) and ``history`` (a ``HistoryConstraints``) -- validated once (``ValueError``): the ranges,
+    and that ``eos_token_id`` is the one ``min_new_tokens`` and the stop sequences were given; without one theirs is
+    used.  Processors and constraints whose ``active`` is False become ``None``, except that constraints keep neutral
+    processors beside them (the history kernel sits on the processors' prologue), as does ``keep_neutral``.
+
+    Derived: ``greedy``, ``inv_temp`` (``fp32(1 / temperature)``) and ``nucleus`` (``top_p`` does something)."""
+
+    def __init__(self, temperature: float = 1.0, top_k=None, top_p=None, eos_token_id=None, processors=None,
+                 history=None, who: str = "sample", keep_neutral: bool = False):
+        if temperature < 0:
+            raise ValueError(f"{who}: temperature must be >= 0")
+        if top_k is not None and top_k < 1:
+            raise ValueError(f"{who}: top_k must be >= 1")
+        self.nucleus = check_top_p(top_p, who)
+        self.temperature, self.top_k, self.top_p = float(temperature), top_k, top_p
+        self.greedy = temperature == 0
+        self.inv_temp = 0.0 if self.greedy else float(np.float32(1.0 / temperature))
+        eos = eos_token_id
+        history = history if history is not None and history.active else None
+        if history is not None:
+            if eos is None:
+                eos = history.eos_token_id
+            elif history.stop_sequences and int(eos) != history.eos_token_id:
+                raise ValueError(f"{who}: eos_token_id differs from the constraints' eos_token_id")
+            if processors is None:
+                processors = LogitProcessors(eos_token_id=eos)
+        elif processors is not None and not (processors.active or keep_neutral):
+            processors = None
+        if processors is not None:
+            if eos is None:
+                eos = processors.eos_token_id
+            elif processors.min_new_tokens > 0 and int(eos) != processors.eos_token_id:
+                raise ValueError(f"{who}: eos_token_id differs from the processors' eos_token_id")
+        self.eos_token_id = None if eos is None else int(eos)
+        self.processors, self.history = processors, history
+        # what the launch is given
+        self._core = (self.inv_temp, self.greedy, 0 if top_k is None else int(top_k), -1 if eos is None else int(eos))
+        self._top_p = float(top_p) if self.nucleus else 0.0
+        self._proc = self._hist = None
+        if processors is not None:
+            self._proc = dict(rep=float(processors.rep), inv_rep=float(processors.inv_rep), freq=float(processors.freq),
+                              pres=float(processors.pres), min_new=processors.min_new_tokens)
+        if history is not None:
+            self._hist = dict(ngram=history.no_repeat_ngram_size, n_ban=len(history.bad_words),
+                              n_stop=len(history.stop_sequences))
+
+    def check(self, B: int, V: int, device=None):
+        """The checks that need the batch and the vocabulary: the members' own, and ``eos_token_id < V``."""
+        if self.eos_token_id is not None and not 0 <= self.eos_token_id < V:
+            raise ValueError("eos_token_id must be a token of the vocabulary")
+        if self.processors is not None:
+            self.processors.check(B, V, device)
+        if self.history is not None:
+            self.history.check(V)
+        return self
+
+    def bias(self, B: int, V: int, Vp: int, device=None):
+        """The merged bias of processors and constraints, fp32 ``[1 or B, Vp]``, or ``None`` without processors or
+        without anything to add."""
+        if self.processors is None:
+            return None
+        bias = self.processors.bias(B, V, Vp, device)
+        return bias if self.history is None else self.history.merge_bias(bias, V, Vp, device)
+
+
+def _sample_cpu(cfg, logits, V, state, next, out, logits_out, T0, counts, bias, processed_out, stop_hit):
+    """The CPU twin of the sampler launch: processors, bans, the choice, the eos and stop rules and the bookkeeping of
+    a generation step on a CPU ``DecodeState``, in the kernel's order."""
+    B = logits.shape[0]
+    eos, hist = cfg._core[3], cfg.history
+    step = state.step()
+    offs = state.offsets(B)
+    was_fin = state.finished[:B].bool() if eos >= 0 else torch.zeros(B, dtype=torch.bool)
+    y = logits
+    if cfg.processors is not None:
+        y = process_logits_reference(logits, V, counts, cfg.processors, step, _bias=bias)
+        if hist is not None:             # a finished row ignores bans: it emits eos
+            ban = history_bans_reference(out, [T0 + off + step for off in offs], V, hist)
+            y[:, :V][ban & ~was_fin[:, None]] = -math.inf
+        if processed_out is not None:
+            processed_out.copy_(y)
+    tok = sample_reference(y, V, state, cfg.temperature, cfg.top_k, top_p=cfg.top_p)
+    if eos >= 0:
+        tok = torch.where(was_fin, torch.full_like(tok, eos), tok)
+        state.finished[:B] = (was_fin | (tok == eos)).int()
+    if hist is not None and hist.stop_sequences:
+        for b, off in enumerate(offs):
+            if was_fin[b]:
+                continue
+            gen = out[b, T0 + off:T0 + off + step].tolist() + [int(tok[b])]
+            for q, seq in enumerate(hist.stop_sequences):
+                if len(gen) >= len(seq) and gen[len(gen) - len(seq):] == seq:
+                    state.finished[b] = 1
+                    stop_hit[b] = q
+                    break
+    next.copy_(tok)
+    for b, off in enumerate(offs):
+        if 0 <= T0 + off + step < out.shape[1]:
+            out[b, T0 + off + step] = tok[b]
+    if logits_out is not None and step < logits_out.shape[1]:
+        logits_out[:, step] = logits[:, :V].to(logits_out.dtype)
+    if cfg.processors is not None:
+        counts.add_(tok)
+    state.advance_()
+    return next
+
+
 def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=None, eos_token_id=None,
            next=None, out=None, logits_out=None, T0: int = 0, threshold_out=None, top_p=None,
            processors=None, counts=None, processed_out=None, _force_proc=False, _bias=None, history=None,
-           stop_hit=None):
+           stop_hit=None, config=None):
     """Sample one token per row of the ``[B, Vp]`` bf16 logits on the device (one block per row).
 
     With a ``DecodeState`` the launch also does the bookkeeping of a generation step: the token goes to
@@ -731,119 +862,111 @@ def sample(logits, V: int, snapshot_or_state, temperature: float = 1.0, top_k=No
     need ``stop_hit`` (int32 ``[B]`` on the logits' device, ``-1`` in rows that have not stopped) and an eos.  The
     constraints run on top of the processors' kernel: without ``processors`` neutral ones are used, and without
     ``counts`` a scratch one.  Constraints whose ``active`` is False change nothing.  CPU tensors run
-    ``history_bans_reference`` and the stop rule with the same bookkeeping."""
-    if temperature < 0:
-        raise ValueError("temperature must be >= 0")
-    if top_k is not None and top_k < 1:
-        raise ValueError("top_k must be >= 1")
-    nucleus = check_top_p(top_p, "sample")
+    ``history_bans_reference`` and the stop rule with the same bookkeeping.
+
+    ``config`` (a ``SamplerConfig``) stands for ``temperature``, ``top_k``, ``top_p``, ``eos_token_id``, ``processors``
+    and ``history``, which are then ignored, and says that the caller has checked the buffers against it, as
+    ``SampleBuffers`` does: nothing is validated again, and ``_bias`` is the merged bias or ``None`` for none."""
     B = logits.shape[0]
-    hist = history is not None and history.active
-    if hist:
-        history.check(V)
-        if out is None or out.dim() != 2 or out.shape[0] != B or out.dtype != torch.int64 or not out.is_contiguous():
-            raise ValueError("sample: history constraints read the rows' histories from `out`, contiguous int64 [B, .]")
-        if eos_token_id is None:
-            eos_token_id = history.eos_token_id
-        elif history.stop_sequences and int(eos_token_id) != history.eos_token_id:
-            raise ValueError("sample: eos_token_id differs from the constraints' eos_token_id")
-        if history.stop_sequences and (stop_hit is None or tuple(stop_hit.shape) != (B,)
-                                       or stop_hit.dtype != torch.int32 or stop_hit.device != logits.device):
-            raise ValueError("sample: stop sequences need `stop_hit`, int32 [B] on the logits' device")
-        if processors is None:
-            processors = LogitProcessors(eos_token_id=eos_token_id)
-        if counts is None and not processors.active:
-            counts = TokenCounts(B, logits.shape[1], logits.device)        # neutral processors read nothing from it
-    proc = hist or (processors is not None and (processors.active or bool(_force_proc)))
-    if proc:
-        if not isinstance(counts, TokenCounts) or tuple(counts.buf.shape) != tuple(logits.shape) \
-                or counts.buf.device != logits.device:
-            raise ValueError("sample: processors need `counts`, a TokenCounts [B, Vp] on the logits' device")
-        if eos_token_id is None:
-            eos_token_id = processors.eos_token_id
-        elif processors.min_new_tokens > 0 and int(eos_token_id) != processors.eos_token_id:
-            raise ValueError("sample: eos_token_id differs from the processors' eos_token_id")
-        bias = _bias
-        if bias is None:
-            bias = processors.bias(B, V, logits.shape[1], logits.device)
-            if hist:
-                bias = history.merge_bias(bias, V, logits.shape[1], logits.device)
-        if processed_out is not None and (tuple(processed_out.shape) != tuple(logits.shape)
-                                          or processed_out.dtype != logits.dtype
-                                          or processed_out.device != logits.device):
-            raise ValueError("sample: processed_out must match the logits' shape, dtype and device")
+    cfg, bias = config, _bias
+    if cfg is None:
+        cfg = SamplerConfig(temperature, top_k, top_p, eos_token_id, processors, history, keep_neutral=_force_proc)
+        if cfg.history is not None:
+            cfg.history.check(V)
+            if out is None or out.dim() != 2 or out.shape[0] != B or out.dtype != torch.int64 \
+                    or not out.is_contiguous():
+                raise ValueError("sample: history constraints read the rows' histories from `out`, contiguous int64 "
+                                 "[B, .]")
+            if cfg.history.stop_sequences and (stop_hit is None or tuple(stop_hit.shape) != (B,)
+                                               or stop_hit.dtype != torch.int32 or stop_hit.device != logits.device):
+                raise ValueError("sample: stop sequences need `stop_hit`, int32 [B] on the logits' device")
+            if counts is None and not cfg.processors.active:
+                counts = TokenCounts(B, logits.shape[1], logits.device)    # neutral processors read nothing from it
+        if cfg.processors is not None:
+            if not isinstance(counts, TokenCounts) or tuple(counts.buf.shape) != tuple(logits.shape) \
+                    or counts.buf.device != logits.device:
+                raise ValueError("sample: processors need `counts`, a TokenCounts [B, Vp] on the logits' device")
+            if bias is None:
+                bias = cfg.bias(B, V, logits.shape[1], logits.device)
+            if processed_out is not None and (tuple(processed_out.shape) != tuple(logits.shape)
+                                              or processed_out.dtype != logits.dtype
+                                              or processed_out.device != logits.device):
+                raise ValueError("sample: processed_out must match the logits' shape, dtype and device")
     if isinstance(snapshot_or_state, DecodeState):
         state = snapshot_or_state
     else:
-        state = DecodeState(logits.device, snapshot_or_state)
+        state = DecodeState(logits.device, snapshot_or_state, rows=MAX_ROWS if logits.is_cuda else max(B, MAX_ROWS))
     if next is None:
         next = torch.zeros(B, device=logits.device, dtype=torch.int64)
     if out is None:
         out = torch.zeros(B, T0 + 1, device=logits.device, dtype=torch.int64)
-    eos = -1 if eos_token_id is None else int(eos_token_id)
     if not logits.is_cuda:
-        step = state.step()
-        y = logits
-        offs = state.row_offsets[:B].tolist() + [0] * max(B - MAX_ROWS, 0)
-        was_fin = state.finished[:B].bool() if eos >= 0 else torch.zeros(B, dtype=torch.bool)
-        if proc:
-            y = process_logits_reference(logits, V, counts, processors, step, _bias=bias)
-            if hist:                     # a finished row ignores bans: it emits eos
-                ban = history_bans_reference(out, [T0 + off + step for off in offs], V, history)
-                y[:, :V][ban & ~was_fin[:, None]] = -math.inf
-            if processed_out is not None:
-                processed_out.copy_(y)
-        tok = sample_reference(y, V, state, temperature, top_k, top_p=top_p)
-        if eos >= 0:
-            fin = was_fin
-            tok = torch.where(fin, torch.full_like(tok, eos), tok)
-            state.finished[:B] = (fin | (tok == eos)).int()
-        if hist and history.stop_sequences:
-            for b, off in enumerate(offs):
-                if was_fin[b]:
-                    continue
-                gen = out[b, T0 + off:T0 + off + step].tolist() + [int(tok[b])]
-                for q, seq in enumerate(history.stop_sequences):
-                    if len(gen) >= len(seq) and gen[len(gen) - len(seq):] == seq:
-                        state.finished[b] = 1
-                        stop_hit[b] = q
-                        break
-        next.copy_(tok)
-        for b, off in enumerate(offs):
-            if 0 <= T0 + off + step < out.shape[1]:
-                out[b, T0 + off + step] = tok[b]
-        if logits_out is not None and step < logits_out.shape[1]:
-            logits_out[:, step] = logits[:, :V].to(logits_out.dtype)
-        if proc:
-            counts.add_(tok)
-        state.advance_()
-        return next
+        return _sample_cpu(cfg, logits, V, state, next, out, logits_out, T0, counts, bias, processed_out, stop_hit)
     if logits.dim() != 2 or logits.dtype != _BF16 or logits.shape[1] % 8 or not logits.is_contiguous():
         raise NotImplementedError("sample: the GPU path takes contiguous bf16 logits [B, Vp] with Vp % 8 == 0")
     if B > MAX_ROWS:
         raise NotImplementedError(f"sample: at most {MAX_ROWS} rows on the GPU (got {B})")
-    greedy = temperature == 0
-    inv_temp = 0.0 if greedy else float(np.float32(1.0 / temperature))
-    if hist:
-        work = torch.empty_like(logits) if processed_out is None else processed_out
-        ban, stop = history.tables(logits.device)
-        kernels().decode_sample_hist(logits, int(V), state.buf, next, out, logits_out, int(T0), inv_temp, greedy,
-                                     0 if top_k is None else int(top_k), eos, threshold_out,
-                                     float(top_p) if nucleus else 0.0, counts.buf, bias, work,
-                                     float(processors.rep), float(processors.inv_rep), float(processors.freq),
-                                     float(processors.pres), processors.min_new_tokens,
-                                     history.no_repeat_ngram_size, ban, len(history.bad_words), stop,
-                                     len(history.stop_sequences), stop_hit if history.stop_sequences else None)
-        return next
-    if proc:
-        work = torch.empty_like(logits) if processed_out is None else processed_out
-        kernels().decode_sample_proc(logits, int(V), state.buf, next, out, logits_out, int(T0), inv_temp, greedy,
-                                     0 if top_k is None else int(top_k), eos, threshold_out,
-                                     float(top_p) if nucleus else 0.0, counts.buf, bias, work,
-                                     float(processors.rep), float(processors.inv_rep), float(processors.freq),
-                                     float(processors.pres), processors.min_new_tokens)
-        return next
-    kernels().decode_sample(logits, int(V), state.buf, next, out, logits_out, int(T0), inv_temp, greedy,
-                            0 if top_k is None else int(top_k), eos, threshold_out,
-                            float(top_p) if nucleus else 0.0)
+    kw = {}
+    if cfg.processors is not None:
+        kw = dict(cfg._proc, counts=counts.buf, bias=bias,
+                  work=torch.empty_like(logits) if processed_out is None else processed_out)
+        if cfg.history is not None:
+            ban, stop = cfg.history.tables(logits.device)
+            kw.update(cfg._hist, ban=ban, stop=stop, stop_hit=stop_hit if stop is not None else None)
+    kernels().decode_sample(logits, int(V), state.buf, next, out, logits_out, int(T0), *cfg._core, threshold_out,
+                            cfg._top_p, **kw)
     return next
+
+
+class SampleBuffers:
+    """What a generation of ``n_new`` tokens after the prompts ``idx`` (``[B, Tin]``; ``lens``: the ``B`` prompt lengths
+    of a ragged batch, or ``None``) keeps between its sampler calls, on either device: the ``DecodeState`` with the
+    rows' offsets (at position ``pos``, default the longest prompt's last), ``next``, ``out`` -- ``[B, Tin + n_new]``,
+    the prompts, and ``pad_token_id`` elsewhere in a ragged batch -- and ``logits_out`` (``[B, n_new, V]`` in ``dtype``
+    with ``return_logits``, else ``None``).  Only when ``config`` has processors (constraints bring neutral ones):
+    ``counts`` with the prompt flags set, the workspace ``work`` and the merged ``bias``; only with stop sequences:
+    ``stop_hit``.  They are ``None`` otherwise.  ``Vp`` is the width of the logits that ``sample`` will be given."""
+
+    def __init__(self, config, idx, lens, n_new, V, Vp, device, rng_state, pad_token_id=0, return_logits=False,
+                 pos=None, dtype=_BF16):
+        dev = torch.device(device)
+        B, Tin = idx.shape
+        self.config, self.V = config, int(V)
+        self.T0 = T0 = Tin if lens is None else max(lens)
+        self.state = DecodeState(dev, rng_state, pos=T0 - 1 if pos is None else pos, step=0,
+                                 row_offsets=None if lens is None else [n - T0 for n in lens],
+                                 rows=MAX_ROWS if dev.type == "cuda" else max(B, MAX_ROWS))
+        if lens is None:
+            self.out = torch.zeros(B, T0 + n_new, device=dev, dtype=torch.int64)
+            self.out[:, :T0] = idx
+        else:
+            real = torch.arange(Tin, device=dev)[None, :] < torch.tensor(lens, device=dev)[:, None]
+            self.out = torch.full((B, Tin + n_new), int(pad_token_id), device=dev, dtype=torch.int64)
+            self.out[:, :Tin] = torch.where(real, idx, self.out[:, :Tin])
+        self.next = torch.zeros(B, device=dev, dtype=torch.int64)
+        self.logits_out = torch.empty(B, n_new, self.V, device=dev, dtype=dtype) if return_logits else None
+        self.counts = self.work = self.bias = self.stop_hit = None
+        if config.processors is not None:    # allocated once; the prompt flags before the first sample
+            self.counts = TokenCounts(B, Vp, dev).add_prompt(idx, self.state, T0=T0)
+            self.work = torch.empty(B, Vp, device=dev, dtype=dtype)
+            self.bias = config.bias(B, self.V, Vp, dev)
+            if config.history is not None and config.history.stop_sequences:
+                self.stop_hit = torch.full((B,), -1, device=dev, dtype=torch.int32)
+
+    def sample(self, logits):
+        """One generation step from the ``[B, Vp]`` logits of the rows' current positions; returns ``next``."""
+        return sample(logits, self.V, self.state, next=self.next, out=self.out, logits_out=self.logits_out, T0=self.T0,
+                      counts=self.counts, processed_out=self.work, _bias=self.bias, stop_hit=self.stop_hit,
+                      config=self.config)
+
+    def _dirty(self):
+        counts = None if self.counts is None else self.counts.buf
+        return [t for t in (self.state.buf, self.next, counts, self.stop_hit) if t is not None]
+
+    def snapshot(self):
+        """Copies of what a step changes besides its own output slot: state, ``next``, counts and ``stop_hit``."""
+        return [t.clone() for t in self._dirty()]
+
+    def restore(self, saved):
+        for t, s in zip(self._dirty(), saved):
+            t.copy_(s)

@@ -242,25 +242,25 @@ def test_stop_sequences(model):
 
 def test_stop_hit_of_the_cpu_sampler(model):
     """``stop_hit`` as the CPU generation keeps it, against the replay's."""
-    from pytorch_distributed_example_amd.models.gpt2 import _CpuProcSampler
     lens, eos = [3, 5, 4], 999
     idx = GC.ragged_prompt(lens)
     lg = torch.full((3, V), -5.0)
     hist = HistoryConstraints(0, None, [[40, 41], [41], [7, 40, 41]], eos)
-    smp = _CpuProcSampler(None, idx, lens, V, DeviceRNG(1), 0.0, None, eos, None, hist, 4)
+    smp = D.SampleBuffers(D.SamplerConfig(0.0, eos_token_id=eos, history=hist), idx, lens, 4, V, V, "cpu",
+                          DeviceRNG(1).state, dtype=torch.float32)
     want = [[7, 40, 41, eos], [41, eos, eos, eos], [7, 7, 40, 7]]
     hits = []
     for s in range(4):
         x = lg.clone()
         for b in range(3):
             x[b, want[b][s]] = 5.0
-        tok = smp(x)
+        tok = smp.sample(x)
         assert tok.tolist() == [want[b][s] for b in range(3)]
         hits.append(smp.stop_hit.tolist())
     assert hits == [[-1, 1, -1], [-1, 1, -1], [0, 1, -1], [0, 1, -1]]
     assert smp.state.finished[:3].tolist() == [1, 1, 0]
     for b, n in enumerate(lens):
-        assert smp.kw["out"][b, n:n + 4].tolist() == want[b]
+        assert smp.out[b, n:n + 4].tolist() == want[b]
 
 
 def test_defaults_are_the_call_as_it_was(model):

@@ -38,14 +38,16 @@ def test_launcher_rejects_invalid_arguments():
     hit = torch.zeros(HR.B, device=dev, dtype=torch.int32)
     tab = torch.tensor([0, 2, 5, 6], device=dev, dtype=torch.int32)
 
-    def call(ngram=2, ban=None, n_ban=0, stop=None, n_stop=0, stop_hit=None, eos=5):
-        D.kernels().decode_sample_hist(lg, HR.V, state.buf, nxt, out, None, c.T0, 0.0, True, 0, eos, None, 0.0, tc.buf,
-                                       None, work, 1.0, 1.0, 0.0, 0.0, 0, ngram, ban, n_ban, stop, n_stop, stop_hit)
+    def call(ngram=2, ban=None, n_ban=0, stop=None, n_stop=0, stop_hit=None, eos=5, counts=tc.buf, work=work):
+        D.kernels().decode_sample(lg, HR.V, state.buf, nxt, out, None, c.T0, 0.0, True, 0, eos, counts=counts, work=work,
+                                  ngram=ngram, ban=ban, n_ban=n_ban, stop=stop, n_stop=n_stop, stop_hit=stop_hit)
 
     call(stop=tab, n_stop=1, stop_hit=hit)                       # a valid call
     for kw in (dict(ngram=HR.MAX_N + 1), dict(ngram=-1), dict(n_ban=1), dict(ban=tab, n_ban=HR.MAX_SEQS + 1),
                dict(stop=tab, n_stop=1), dict(stop=tab, n_stop=1, stop_hit=hit, eos=-1),
-               dict(stop=tab.long(), n_stop=1, stop_hit=hit), dict(ban=tab, n_ban=2)):
+               dict(stop=tab.long(), n_stop=1, stop_hit=hit), dict(ban=tab, n_ban=2),
+               dict(counts=None), dict(ngram=0, counts=None),    # a group given in part: work without counts ...
+               dict(counts=None, work=None)):                    # ... and history arguments without the processors'
         with pytest.raises(RuntimeError):
             call(**kw)
     with pytest.raises(ValueError):                              # stop sequences need stop_hit on the device
