@@ -120,7 +120,7 @@ void gelu_bwd(const at::Tensor& dY, const at::Tensor& X, const at::Tensor& dX) {
 
 // scale_dev (fp32 [1], e.g. the inv word of loss_targets' info block): the masked-loss kernels.
 // label_smoothing / z_loss / loss_weights (fp32 [N]): any of them away from 0 / 0 / None selects the smoothed and
-// weighted kernels (PdeXentSmooth in pde_kernels.h), which need scale_dev.
+// weighted kernels (a non-null PdeXentSmooth for pde_xent_bf16, pde_kernels.h), which need scale_dev.
 void xent_bf16(const at::Tensor& logits, const at::Tensor& tgt, int64_t V, double scale, const at::Tensor& loss_rows,
                bool write_grad, const OptT& scale_dev, double label_smoothing, double z_loss,
                const OptT& loss_weights) {
@@ -136,22 +136,19 @@ void xent_bf16(const at::Tensor& logits, const at::Tensor& tgt, int64_t V, doubl
                   (sd == nullptr || scale_dev->device() == logits.device()),
               "xent_bf16: all tensors must be on the logits' device");
   const float* wp = optr<float>(loss_weights, "loss_weights", F32, N);
-  if (wp == nullptr && label_smoothing == 0.0 && z_loss == 0.0) {
-    hip_check(pde_xent_bf16(logits.data_ptr(), ptr<int64_t>(tgt), (int)N, (int)Vp, (int)V, (float)scale,
-                            ptr<float>(loss_rows), write_grad, sd, cur_stream()),
-              "xent_bf16");
-    return;
+  const bool smooth = wp != nullptr || label_smoothing != 0.0 || z_loss != 0.0;
+  if (smooth) {
+    TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "xent_bf16: label_smoothing must be in [0, 1), got ",
+                label_smoothing);
+    TORCH_CHECK(z_loss >= 0.0 && std::isfinite(z_loss), "xent_bf16: z_loss must be finite and >= 0, got ", z_loss);
+    TORCH_CHECK(sd != nullptr, "xent_bf16: the smoothed and weighted loss needs scale_dev");
+    TORCH_CHECK(V >= 1, "xent_bf16: the smoothed and weighted loss needs V >= 1");
+    TORCH_CHECK(wp == nullptr || (loss_weights->numel() == N && loss_weights->device() == logits.device()),
+                "xent_bf16: loss_weights must hold N floats on the logits' device");
   }
-  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "xent_bf16: label_smoothing must be in [0, 1), got ",
-              label_smoothing);
-  TORCH_CHECK(z_loss >= 0.0 && std::isfinite(z_loss), "xent_bf16: z_loss must be finite and >= 0, got ", z_loss);
-  TORCH_CHECK(sd != nullptr, "xent_bf16: the smoothed and weighted loss needs scale_dev");
-  TORCH_CHECK(V >= 1, "xent_bf16: the smoothed and weighted loss needs V >= 1");
-  TORCH_CHECK(wp == nullptr || (loss_weights->numel() == N && loss_weights->device() == logits.device()),
-              "xent_bf16: loss_weights must hold N floats on the logits' device");
   const PdeXentSmooth sm{wp, (float)(1.0 - label_smoothing), (float)(label_smoothing / (double)V), (float)z_loss};
-  hip_check(pde_xent_bf16_smooth(logits.data_ptr(), ptr<int64_t>(tgt), (int)N, (int)Vp, (int)V, (float)scale,
-                                 ptr<float>(loss_rows), write_grad, sd, sm, cur_stream()),
+  hip_check(pde_xent_bf16(logits.data_ptr(), ptr<int64_t>(tgt), (int)N, (int)Vp, (int)V, (float)scale,
+                          ptr<float>(loss_rows), write_grad, sd, smooth ? &sm : nullptr, cur_stream()),
             "xent_bf16");
 }
 

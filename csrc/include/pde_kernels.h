@@ -154,12 +154,11 @@ hipError_t pde_ln_bwd(const void* dY, const void* X, const float* mean, const fl
                       PdeDrop drop, void* dD, hipStream_t st);
 hipError_t pde_gelu_fwd(const void* X, void* Y, int64_t n, hipStream_t st);
 hipError_t pde_gelu_bwd(const void* dY, const void* X, void* dX, int64_t n, hipStream_t st);
-// scale_dev (nullable, fp32 [1], pde_loss.h): the masked-loss instantiations -- the gradient scale is
-// scale * scale_dev[0] and a row whose target is outside [0, V) is zeroed without being read
-hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
-                         int write_grad, const float* scale_dev, hipStream_t st);
-// Smoothed and weighted loss: the SMOOTH instantiations (they imply the masked-loss ones' early exit and
-// scale_dev, which is required).  With lse and p the row's log-sum-exp and softmax over the V real columns:
+// The fused softmax-CE of the LM head, one entry.  scale_dev (nullable, fp32 [1], pde_loss.h): the masked-loss
+// instantiations -- the gradient scale is scale * scale_dev[0] and a row whose target is outside [0, V) is zeroed
+// without being read.  sm (nullable): the SMOOTH instantiations of the smoothed and weighted loss (they imply the
+// masked-loss ones' early exit and scale_dev, which is required).  With lse and p the row's log-sum-exp and softmax
+// over the V real columns:
 //   loss_rows[i]  = w[i] * (lse - keep * x[t] - spread * sum_{v<V} x[v] + z * lse^2)
 //   dlogits[i, v] = w[i] * scale * scale_dev[0] * ((1 + 2 z lse) p[v] - keep [v == t] - spread)      v < V
 // and exact zeros in the columns >= V and in the rows whose target is outside [0, V), whose weight is not read.
@@ -169,8 +168,8 @@ typedef struct PdeXentSmooth {
   float spread;     // label_smoothing / V
   float z;          // z-loss coefficient
 } PdeXentSmooth;
-hipError_t pde_xent_bf16_smooth(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
-                                int write_grad, const float* scale_dev, PdeXentSmooth sm, hipStream_t st);
+hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
+                         int write_grad, const float* scale_dev, const PdeXentSmooth* sm, hipStream_t st);
 // doc_start / doc_end (nullable, int32 [N]): packed sequences.  The forward reads wpe[t - doc_start[row]],
 // the backward sums dX into dwpe by that position, walking each row's documents through doc_end.
 hipError_t pde_embed_fwd(const int64_t* idx, const void* wte, const void* wpe, void* out, int N, int T, int C,

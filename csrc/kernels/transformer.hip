@@ -1247,11 +1247,13 @@ hipError_t pde_gelu_bwd(const void* dY, const void* X, void* dX, int64_t n, hipS
   return hipGetLastError();
 }
 
-// scale_dev (nullable): the MASK instantiations (scale * scale_dev[0], ignored rows leave early); smooth: the
-// SMOOTH ones, which need scale_dev.  The routes are the same for all three.
-static hipError_t xent_bf16_launch(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale,
-                                   float* loss_rows, int write_grad, const float* scale_dev, bool smooth,
-                                   PdeXentSmooth sm, hipStream_t st) {
+// scale_dev (nullable): the MASK instantiations (scale * scale_dev[0], ignored rows leave early); smp (nullable): the
+// SMOOTH ones, which need scale_dev.  The routes are the same for all three, and so is the kernels' argument list:
+// without smp they get a neutral struct that they never load.
+hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
+                         int write_grad, const float* scale_dev, const PdeXentSmooth* smp, hipStream_t st) {
+  const bool smooth = smp != nullptr;
+  const PdeXentSmooth sm = smooth ? *smp : PdeXentSmooth{nullptr, 1.f, 0.f, 0.f};
   if (smooth && !scale_dev) return hipErrorInvalidValue;
   if (N == 0) return hipSuccess;
 #define XENT_AS(K, MASK, SMOOTH)                                                                                \
@@ -1283,17 +1285,6 @@ static hipError_t xent_bf16_launch(void* logits, const int64_t* tgt, int N, int 
 #undef XENT
 #undef XENT_AS
   return hipGetLastError();
-}
-
-hipError_t pde_xent_bf16(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
-                         int write_grad, const float* scale_dev, hipStream_t st) {
-  return xent_bf16_launch(logits, tgt, N, Vp, V, scale, loss_rows, write_grad, scale_dev, false,
-                          PdeXentSmooth{nullptr, 1.f, 0.f, 0.f}, st);
-}
-
-hipError_t pde_xent_bf16_smooth(void* logits, const int64_t* tgt, int N, int Vp, int V, float scale, float* loss_rows,
-                                int write_grad, const float* scale_dev, PdeXentSmooth sm, hipStream_t st) {
-  return xent_bf16_launch(logits, tgt, N, Vp, V, scale, loss_rows, write_grad, scale_dev, true, sm, st);
 }
 
 hipError_t pde_loss_targets(PdeLossTargets a, hipStream_t st) {

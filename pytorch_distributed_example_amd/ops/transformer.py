@@ -580,38 +580,75 @@ def embedding(idx, wte, wpe, p: float = 0.0, rng_snapshot=None, site: int = 0, d
 
 
 # --------------------------------------------------------------------------------------- LM head + CE
-class LMHeadLossFn(torch.autograd.Function):
-    """mean cross-entropy of logits = h @ W^T over the first V columns of W ([Vp, C], padded vocab).
+class _LossSpec(NamedTuple):
+    """``lm_head_loss``'s keywords, validated once: all that the launch and the CPU rows read."""
+    eps: float          # label_smoothing
+    zc: float           # z_loss
+    weights: object     # loss_weights as a contiguous flat fp32 vector, or None
+    reduction: str
+    smooth: bool        # eps, zc or weights away from 0 / 0 / None: the SMOOTH kernels
+    plain: bool         # every keyword at its default: the call as it was, without loss_targets
 
-    Forward runs the GEMM and the fused softmax-CE kernel, which overwrites the logits buffer with
-    dlogits = (softmax - onehot) / N (masked loss: times ``inv[0]``, a device value, and exact zeros in
-    rows that do not count; ``smooth = (label_smoothing, z_loss, weights or None)``: the smoothed and weighted
-    gradient of ``lm_head_loss``, still written by the same kernel); backward is two GEMMs from that buffer with the incoming loss
+
+def _loss_spec(targets, ignore_index, loss_mask, doc_bounds, mask_doc_ends, reduction, denom, label_smoothing, z_loss,
+               loss_weights):
+    try:
+        eps, zc = float(label_smoothing), float(z_loss)
+    except (TypeError, ValueError):
+        raise ValueError(f"lm_head_loss: label_smoothing and z_loss must be numbers, got {label_smoothing!r} and "
+                         f"{z_loss!r}") from None
+    if not (math.isfinite(eps) and 0.0 <= eps < 1.0):
+        raise ValueError(f"lm_head_loss: label_smoothing must be in [0, 1), got {label_smoothing!r}")
+    if not (math.isfinite(zc) and zc >= 0.0):
+        raise ValueError(f"lm_head_loss: z_loss must be finite and >= 0, got {z_loss!r}")
+    wts = None
+    if loss_weights is not None:
+        if not (torch.is_tensor(loss_weights) and loss_weights.is_floating_point()):
+            raise ValueError(f"lm_head_loss: loss_weights must be a floating tensor, got "
+                             f"{getattr(loss_weights, 'dtype', type(loss_weights))} (a 0/1 selection is loss_mask)")
+        if tuple(loss_weights.shape) != tuple(targets.shape) or loss_weights.device != targets.device:
+            raise ValueError(f"lm_head_loss: loss_weights must have the targets' shape and device (got "
+                             f"{tuple(loss_weights.shape)} on {loss_weights.device})")
+        wts = _c(loss_weights.detach().reshape(-1).float())
+    smooth = eps != 0.0 or zc != 0.0 or wts is not None
+    plain = (ignore_index is None and loss_mask is None and doc_bounds is None and not mask_doc_ends
+             and reduction == "mean" and denom is None and not smooth)
+    return _LossSpec(eps, zc, wts, reduction, smooth, plain)
+
+
+def _lm_head_xent(h2, w, tg, V, spec, inv, write_grad):
+    """The one launch path of the LM head loss: the GEMM and the softmax-CE kernel over its logits.  ``tg``: flat int64
+    targets; ``tg`` and ``inv`` are ``loss_targets``' unless ``spec.plain`` (then ``inv`` is None).  Returns the logits
+    (dlogits after ``write_grad``), the fp32 loss rows and the scale keywords for the ``sum_f32`` that reduces them."""
+    N = h2.shape[0]
+    rows = torch.empty(N, device=h2.device, dtype=torch.float32)
+    # [N, Vp] bf16 logits on the own persistent GEMM; 1.65 GB at GPT-2 shapes, stored non-temporally
+    # (read back once, by the cross-entropy right after) so they do not evict the operand tiles
+    logits = G.fprop(h2, w, nt_out=True)
+    # plain: the host's 1 / N (a negative target is a zero row that counts in N); else the device's inv
+    scale = dict(scale=1.0 / N) if spec.plain else dict(scale=1.0, scale_dev=inv)
+    smooth = dict(label_smoothing=spec.eps, z_loss=spec.zc, loss_weights=spec.weights) if spec.smooth else {}
+    kernels().xent_bf16(logits, tg, V, loss_rows=rows, write_grad=write_grad, **scale, **smooth)
+    return logits, rows, scale
+
+
+class LMHeadLossFn(torch.autograd.Function):
+    """The scalar loss of ``lm_head_loss`` over the first V columns of W ([Vp, C], padded vocab), for one ``spec``.
+
+    Forward is ``_lm_head_xent`` with ``write_grad`` -- the logits buffer is overwritten with dlogits: (softmax -
+    onehot) / N when plain; times ``inv[0]`` with exact zeros in rows that do not count when masked; the smoothed
+    and weighted gradient of ``lm_head_loss`` when ``spec.smooth`` -- and one ``sum_f32`` of the rows under the same
+    scale.  Backward is two GEMMs from that buffer with the incoming loss
     gradient applied in their epilogues (a device scalar: no host read, no extra kernel, graph-safe,
     and the saved dlogits stay unscaled, so a retained graph can run backward again).  With W tied to
     the embedding of the same forward pass, dW is left for the embedding backward to accumulate into."""
 
     @staticmethod
-    def forward(ctx, h, w, targets, V, inv=None, smooth=None):
-        C = h.shape[-1]
-        h2 = _c(h.reshape(-1, C))
-        N = h2.shape[0]
-        rows = torch.empty(N, device=h.device, dtype=torch.float32)
-        tg = _c(targets.reshape(-1).long())
-        # [N, Vp] bf16 logits on the own persistent GEMM; 1.65 GB at GPT-2 shapes, stored non-temporally
-        # (read back once, by the cross-entropy right after) so they do not evict the operand tiles
-        logits = G.fprop(h2, w, nt_out=True)
+    def forward(ctx, h, w, targets, V, spec, inv=None):
+        h2 = _c(h.reshape(-1, h.shape[-1]))
+        logits, rows, scale = _lm_head_xent(h2, w, _c(targets.reshape(-1).long()), V, spec, inv, True)
         tot = torch.empty(1, device=h.device, dtype=torch.float32)
-        if inv is None:
-            kernels().xent_bf16(logits, tg, V, 1.0 / N, rows, True)
-            kernels().sum_f32(rows, tot, 1.0 / N)               # mean loss, no separate divide
-        elif smooth is None:   # masked loss: targets are loss_targets' effective ones, inv its device-side 1 / denominator
-            kernels().xent_bf16(logits, tg, V, 1.0, rows, True, scale_dev=inv)
-            kernels().sum_f32(rows, tot, 1.0, scale_dev=inv)
-        else:   # the rows come out weighted, so the sum is the masked loss's
-            kernels().xent_bf16(logits, tg, V, 1.0, rows, True, scale_dev=inv, label_smoothing=smooth[0],
-                                z_loss=smooth[1], loss_weights=smooth[2])
-            kernels().sum_f32(rows, tot, 1.0, scale_dev=inv)
+        kernels().sum_f32(rows, tot, **scale)               # the scale is in the sum: no separate divide
         ctx.save_for_backward(h2, w, logits)
         ctx.hshape = h.shape
         ctx.tied = getattr(w, "_pde_tied_slot", None)
@@ -632,29 +669,6 @@ class LMHeadLossFn(torch.autograd.Function):
         if ctx.tied is not None:
             ctx.tied["dw"] = dw                              # the tied embedding adds its part in place
         return dh.reshape(ctx.hshape), dw, None, None, None, None
-
-
-def _check_smoothing(label_smoothing, z_loss, loss_weights, targets):
-    """``(eps, zc, weights)`` of ``lm_head_loss``, validated: two host floats and the weights as a contiguous fp32
-    vector (or None)."""
-    try:
-        eps, zc = float(label_smoothing), float(z_loss)
-    except (TypeError, ValueError):
-        raise ValueError(f"lm_head_loss: label_smoothing and z_loss must be numbers, got {label_smoothing!r} and "
-                         f"{z_loss!r}") from None
-    if not (math.isfinite(eps) and 0.0 <= eps < 1.0):
-        raise ValueError(f"lm_head_loss: label_smoothing must be in [0, 1), got {label_smoothing!r}")
-    if not (math.isfinite(zc) and zc >= 0.0):
-        raise ValueError(f"lm_head_loss: z_loss must be finite and >= 0, got {z_loss!r}")
-    if loss_weights is None:
-        return eps, zc, None
-    if not (torch.is_tensor(loss_weights) and loss_weights.is_floating_point()):
-        raise ValueError(f"lm_head_loss: loss_weights must be a floating tensor, got "
-                         f"{getattr(loss_weights, 'dtype', type(loss_weights))} (a 0/1 selection is loss_mask)")
-    if tuple(loss_weights.shape) != tuple(targets.shape) or loss_weights.device != targets.device:
-        raise ValueError(f"lm_head_loss: loss_weights must have the targets' shape and device (got "
-                         f"{tuple(loss_weights.shape)} on {loss_weights.device})")
-    return eps, zc, _c(loss_weights.detach().reshape(-1).float())
 
 
 def lm_head_loss(h, w, targets, V: int, *, ignore_index=None, loss_mask=None, doc_bounds=None, mask_doc_ends=False,
@@ -694,59 +708,53 @@ def lm_head_loss(h, w, targets, V: int, *, ignore_index=None, loss_mask=None, do
     * ``eps`` and ``zc`` are host floats, frozen into a captured launch as dropout's ``p`` is; ``loss_weights``
       is device data and follows every replay.
     * Any value away from these defaults runs ``loss_targets`` and the ``SMOOTH`` kernels, also without a mask:
-      every in-range row is then valid and ``inv = 1 / N``.  ``reduction="none"`` returns ``row_i``."""
-    eps, zc, wts = _check_smoothing(label_smoothing, z_loss, loss_weights, targets)
-    smooth = eps != 0.0 or zc != 0.0 or wts is not None
-    if (ignore_index is None and loss_mask is None and doc_bounds is None and not mask_doc_ends
-            and reduction == "mean" and denom is None and not smooth):
-        if _gpu(h):
-            return LMHeadLossFn.apply(h, w, targets, V)
-        logits = torch.matmul(h, w.t())[..., :V].float()
-        return F.cross_entropy(logits.reshape(-1, V), targets.reshape(-1))
-    lt = loss_targets(targets, vocab_size=V, ignore_index=ignore_index, loss_mask=loss_mask, doc_bounds=doc_bounds,
-                      mask_doc_ends=mask_doc_ends, reduction=reduction, denom=denom)
-    if reduction == "none" and torch.is_grad_enabled() and (h.requires_grad or w.requires_grad):
-        raise NotImplementedError("lm_head_loss: reduction='none' has no backward; call it under torch.no_grad()")
-    if _gpu(h):
-        if reduction != "none":
-            if smooth:
-                return LMHeadLossFn.apply(h, w, lt.targets, V, lt.inv, (eps, zc, wts))
-            return LMHeadLossFn.apply(h, w, lt.targets, V, lt.inv)
-        C = h.shape[-1]
-        h2 = _c(h.reshape(-1, C))
-        rows = torch.empty(h2.shape[0], device=h.device, dtype=torch.float32)
-        # loss only (write_grad = 0): the logits stay as they are, ignored rows are not read
-        if smooth:
-            kernels().xent_bf16(G.fprop(h2, w, nt_out=True), _c(lt.targets.reshape(-1)), V, 1.0, rows, False,
-                                scale_dev=lt.inv, label_smoothing=eps, z_loss=zc, loss_weights=wts)
-        else:
-            kernels().xent_bf16(G.fprop(h2, w, nt_out=True), _c(lt.targets.reshape(-1)), V, 1.0, rows, False,
-                                scale_dev=lt.inv)
-        return rows.view(h.shape[:-1])
-    eff = lt.targets.reshape(-1)
-    valid = eff >= 0
-    if smooth:
-        x = torch.matmul(h, w.t())[..., :V].reshape(-1, V)
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.float()
-        # as below: an invalid row (and its weight) is taken out before anything is computed from it
-        x = torch.where(valid[:, None], x, x.new_zeros(()))
+      every in-range row is then valid and ``inv = 1 / N``.  ``reduction="none"`` returns ``row_i``.
+
+    Host path: the keywords become one ``_LossSpec``; the GPU runs ``_lm_head_xent`` (the GEMM and one ``xent_bf16``
+    whose scale and smoothing keywords come from the spec), under ``LMHeadLossFn`` or, for ``"none"``, without
+    ``write_grad``; CPU tensors run ``_cpu_lm_head_loss``."""
+    spec = _loss_spec(targets, ignore_index, loss_mask, doc_bounds, mask_doc_ends, reduction, denom, label_smoothing,
+                      z_loss, loss_weights)
+    tg, inv = targets, None
+    if not spec.plain:
+        lt = loss_targets(targets, vocab_size=V, ignore_index=ignore_index, loss_mask=loss_mask,
+                          doc_bounds=doc_bounds, mask_doc_ends=mask_doc_ends, reduction=reduction, denom=denom)
+        tg, inv = lt.targets, lt.inv
+        if reduction == "none" and torch.is_grad_enabled() and (h.requires_grad or w.requires_grad):
+            raise NotImplementedError("lm_head_loss: reduction='none' has no backward; call it under torch.no_grad()")
+    if not _gpu(h):
+        return _cpu_lm_head_loss(h, w, tg, V, spec, inv)
+    if reduction != "none":
+        return LMHeadLossFn.apply(h, w, tg, V, spec, inv)
+    # loss only (write_grad = 0): the logits stay as they are, ignored rows are not read
+    rows = _lm_head_xent(_c(h.reshape(-1, h.shape[-1])), w, _c(tg.reshape(-1)), V, spec, inv, False)[1]
+    return rows.view(h.shape[:-1])
+
+
+def _cpu_lm_head_loss(h, w, targets, V, spec, inv):
+    """The CPU definition of ``lm_head_loss``: ``targets`` and ``inv`` as ``LMHeadLossFn`` takes them."""
+    x = torch.matmul(h, w.t())[..., :V].reshape(-1, V)
+    # a wart kept as it is: the smoothed rows stay fp64 for fp64 inputs, every other flavour computes in fp32
+    if not (spec.smooth and x.dtype == torch.float64):
+        x = x.float()
+    tg = targets.reshape(-1)
+    if spec.plain:      # all N rows count, and an out-of-range target raises
+        return F.cross_entropy(x, tg)
+    valid = tg >= 0
+    # a row that does not count (and its weight) is zeros before anything is computed from it: NaN cannot leak
+    x = torch.where(valid[:, None], x, x.new_zeros(()))
+    if not spec.smooth:
+        rows = F.cross_entropy(x, tg, ignore_index=-1, reduction="none")
+    else:   # not F.cross_entropy's bits at eps = zc = 0 (lse - x[t] rounds differently), so the two forms stay
         lse = torch.logsumexp(x, 1)
-        xt = x.gather(1, eff.clamp(min=0)[:, None])[:, 0]
-        rows = lse - (1.0 - eps) * xt - (eps / V) * x.sum(1) + zc * lse * lse
-        if wts is not None:
-            rows = rows * torch.where(valid, wts, wts.new_zeros(())).to(x.dtype)
+        xt = x.gather(1, tg.clamp(min=0)[:, None])[:, 0]
+        rows = lse - (1.0 - spec.eps) * xt - (spec.eps / V) * x.sum(1) + spec.zc * lse * lse
+        if spec.weights is not None:
+            rows = rows * torch.where(valid, spec.weights, spec.weights.new_zeros(())).to(x.dtype)
         rows = torch.where(valid, rows, rows.new_zeros(()))
-        if reduction == "none":
-            return rows.view(h.shape[:-1])
-        return rows.sum() * lt.inv
-    logits = torch.matmul(h, w.t())[..., :V].float().reshape(-1, V)
-    # an ignored row counts as zeros whatever it holds: taken out before the softmax, so NaN cannot leak
-    logits = torch.where(valid[:, None], logits, logits.new_zeros(()))
-    rows = F.cross_entropy(logits, eff, ignore_index=-1, reduction="none")
-    if reduction == "none":
+    if spec.reduction == "none":
         return rows.view(h.shape[:-1])
-    return rows.sum() * lt.inv
+    return rows.sum() * inv
 
 
 def lm_logits(h, w, V: int):

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from pytorch_distributed_example_amd import ops
 from pytorch_distributed_example_amd._ext import kernels
 from pytorch_distributed_example_amd.models import GPTConfig, build_gpt2
+from pytorch_distributed_example_amd.ops import gemm as G
 from pytorch_distributed_example_amd.ops import transformer as TR
 
 import masked_loss_ref as M
@@ -258,6 +259,54 @@ def test_masked_lm_head_loss_zero_count(N, V, Vp, C):
         loss.backward()
         assert loss.item() == 0.0
         assert torch.equal(h.grad, torch.zeros_like(h)) and torch.equal(w.grad, torch.zeros_like(w))
+
+
+@pytest.mark.parametrize("N,V,Vp,C", OP_SHAPES)
+def test_every_flavour_is_its_launches_written_out(N, V, Vp, C):
+    """Plain, masked and smoothed, ``mean`` and ``none``: the op's result has the bits of ``G.fprop`` +
+    ``xent_bf16`` + ``sum_f32`` called here with the arguments the host path is documented to pass (plain: the
+    host's ``1 / N``; otherwise ``scale = 1`` with ``loss_targets``' ``inv`` as ``scale_dev``, and the three
+    smoothing keywords only when something is smoothed).  ``dh`` of the ``mean`` calls is compared with the dgrad
+    GEMM of the ``dlogits`` written here, which pins the scale inside the CE kernel too.  One target is ``-1``:
+    with default keywords its row is zero and still counts in ``N``: ``loss * N`` is the sum of the rows to 1e-5
+    (an fp32 sum of ``N <= 37`` positive terms is off by at most ``N * 2^-24 = 2.2e-6``; dividing by the count
+    ``N - 1`` instead would be off by ``1 / N >= 2.7e-2``)."""
+    h, w, tg = _op_inputs(N, V, Vp, C, seed=29)
+    tg[N // 2] = -1
+    tg = tg.to(dev)
+    mask = (torch.arange(N) % 3 != 0).to(dev)
+    wt = (2 * torch.rand(N, generator=torch.Generator().manual_seed(30))).to(dev)
+    sm = dict(label_smoothing=0.1, z_loss=1e-3, loss_weights=wt)
+    K = kernels()
+    one = torch.ones(1, device=dev)
+
+    def written_out(targets, write_grad, scale, **smooth):
+        logits = G.fprop(h.detach(), w.detach(), nt_out=True)
+        rows, tot = torch.empty(N, device=dev), torch.empty(1, device=dev)
+        K.xent_bf16(logits, targets, V, loss_rows=rows, write_grad=write_grad, **scale, **smooth)
+        K.sum_f32(rows, tot, **scale)
+        return rows, tot.reshape(()), (G.dgrad(logits, w.detach(), scale=one) if write_grad else None)
+
+    for name, kw, smooth in (("plain", {}, {}), ("masked", dict(loss_mask=mask), {}), ("smoothed", sm, sm)):
+        if name == "plain":
+            targets, scale = tg, dict(scale=1.0 / N)
+        else:
+            lt = ops.loss_targets(tg, vocab_size=V, loss_mask=kw.get("loss_mask"))
+            targets, scale = lt.targets, dict(scale=1.0, scale_dev=lt.inv)
+        loss = TR.lm_head_loss(h, w, tg, V, **kw)
+        dh, = torch.autograd.grad(loss, h)
+        rows, tot, dh_ref = written_out(targets, True, scale, **smooth)
+        assert torch.equal(loss.detach(), tot) and torch.equal(dh, dh_ref), name
+        assert rows[N // 2].item() == 0.0 and not dh[N // 2].any(), name
+        if name == "plain":     # the -1 row counts in the mean's denominator: sum / N, not sum / (N - 1)
+            total = rows.double().sum().item()
+            assert rows.count_nonzero().item() == N - 1 and abs(loss.item() * N - total) <= 1e-5 * total
+        # reduction="none" is not a default: without other keywords it is the masked flavour with every row selected
+        with torch.no_grad():
+            per = TR.lm_head_loss(h, w, tg, V, reduction="none", **kw)
+        lt = ops.loss_targets(tg, vocab_size=V, loss_mask=kw.get("loss_mask"), reduction="none")
+        rows = written_out(lt.targets, False, dict(scale=1.0, scale_dev=lt.inv), **smooth)[0]
+        assert per.shape == (N,) and torch.equal(per, rows), name
 
 
 # --------------------------------------------------------------------------------------- replay
