@@ -248,6 +248,141 @@ void count_prompt(const at::Tensor& idx, const at::Tensor& state, const at::Tens
             "count_prompt");
 }
 
+// ------------------------------------------------------------------------------------------ beam search
+// table: uint8 [2, PDE_DS_MAX_ROWS, stride], stride % 4 == 0
+int table_stride(const at::Tensor& table, int64_t Tmax) {
+  check_cuda(table, "beam table", at::kByte);
+  TORCH_CHECK(table.dim() == 3 && table.size(0) == 2 && table.size(1) == PDE_DS_MAX_ROWS && table.size(2) >= Tmax &&
+                  table.size(2) % 4 == 0,
+              "beam table must be uint8 [2, ", PDE_DS_MAX_ROWS, ", stride >= Tmax = ", Tmax, "], stride % 4 == 0");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(table.data_ptr()) % 4 == 0, "beam table must be 4-byte aligned");
+  return (int)table.size(2);
+}
+
+void decode_attention_beam(const at::Tensor& qkv, const at::Tensor& cache, const at::Tensor& state,
+                           const at::Tensor& part, const at::Tensor& out, int64_t H, double scale,
+                           const at::Tensor& table) {
+  TORCH_CHECK(qkv.dim() == 2 && H >= 1 && qkv.size(1) == 3 * H * 64, "decode_attention: qkv must be [B, 3 * H * 64]");
+  const int64_t B = qkv.size(0);
+  TORCH_CHECK(B >= 1 && B <= PDE_DS_MAX_ROWS, "decode_attention: 1 <= B <= ", PDE_DS_MAX_ROWS, ", got ", B);
+  check_cuda(qkv, "qkv", BF16);
+  check_al16(qkv, "qkv");
+  check_cache(cache, B, H);
+  const int64_t Tmax = cache.size(3), nch = (Tmax + pde_decode_attn_chunk() - 1) / pde_decode_attn_chunk();
+  check_state(state);
+  check_cuda(part, "part", F32, B * H * nch * 66);
+  check_cuda(out, "out", BF16, B * H * 64);
+  PdeBeamTable t{};
+  t.stride = table_stride(table, Tmax);
+  t.anc = static_cast<const unsigned char*>(table.data_ptr());
+  hip_check(pde_decode_attention_beam(qkv.data_ptr(), cache.data_ptr(), ptr<int>(state), ptr<float>(part),
+                                      out.data_ptr(), (int)B, (int)H, (int)Tmax, (float)scale, t, cur_stream()),
+            "decode_attention");
+}
+
+// One beam step (PdeBeam in pde_decode.h).  logits: bf16 [R = B * K, Vp]; score fp32 [R]; len int32 [R]; cand_score /
+// cand_tok: fp32 / int32 [R, K] workspaces; the traces [max_new, R]; logits_out: bf16 [R, max_new, V] or None.
+void beam_step(const at::Tensor& logits, int64_t V, int64_t K, const at::Tensor& state, const at::Tensor& next,
+               const at::Tensor& score, const at::Tensor& len, const at::Tensor& cand_score,
+               const at::Tensor& cand_tok, const at::Tensor& table, int64_t Tmax, const at::Tensor& tok_trace,
+               const at::Tensor& parent_trace, const at::Tensor& score_trace, const OptT& logits_out, int64_t eos) {
+  check_cuda(logits, "logits", BF16);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) % 8 == 0, "beam_step: logits must be [R, Vp] with Vp % 8 == 0");
+  const int64_t R = logits.size(0), Vp = logits.size(1);
+  TORCH_CHECK(K >= 1 && R >= 1 && R <= PDE_DS_MAX_ROWS && R % K == 0, "beam_step: R = B * K <= ", PDE_DS_MAX_ROWS,
+              " rows, got R ", R, ", K ", K);
+  TORCH_CHECK(V >= K && V <= Vp && eos >= -1 && eos < V, "beam_step: K <= V <= Vp and eos in [-1, V)");
+  check_al16(logits, "logits");
+  check_state(state);
+  check_cuda(next, "next", I64, R);
+  check_cuda(score, "score", F32, R);
+  check_cuda(len, "len", I32, R);
+  check_cuda(cand_score, "cand_score", F32, R * K);
+  check_cuda(cand_tok, "cand_tok", I32, R * K);
+  TORCH_CHECK(Tmax >= 1 && tok_trace.dim() == 2 && tok_trace.size(1) == R, "beam_step: traces must be [max_new, R]");
+  const int64_t max_new = tok_trace.size(0);
+  check_cuda(tok_trace, "tok_trace", I32, max_new * R);
+  check_cuda(parent_trace, "parent_trace", I32, max_new * R);
+  check_cuda(score_trace, "score_trace", F32, max_new * R);
+  PdeBeam a{};
+  a.logits = logits.data_ptr();
+  a.state = ptr<int>(state);
+  a.next = ptr<int64_t>(next);
+  a.score = ptr<float>(score);
+  a.len = ptr<int>(len);
+  a.cand_score = ptr<float>(cand_score);
+  a.cand_tok = ptr<int>(cand_tok);
+  a.stride = table_stride(table, Tmax);
+  a.anc = static_cast<unsigned char*>(table.data_ptr());
+  a.tok_trace = ptr<int>(tok_trace);
+  a.parent_trace = ptr<int>(parent_trace);
+  a.score_trace = ptr<float>(score_trace);
+  a.logits_out = nullptr;
+  if (given(logits_out)) {
+    check_cuda(*logits_out, "logits_out", BF16, R * max_new * V);
+    TORCH_CHECK(logits_out->dim() == 3 && logits_out->size(0) == R && logits_out->size(1) == max_new &&
+                    logits_out->size(2) == V,
+                "beam_step: logits_out must be [R, max_new, V]");
+    a.logits_out = logits_out->data_ptr();
+  }
+  a.B = (int)(R / K);
+  a.K = (int)K;
+  a.V = (int)V;
+  a.Vp = (int)Vp;
+  a.Tmax = (int)Tmax;
+  a.max_new = (int)max_new;
+  a.eos = (int)eos;
+  hip_check(pde_beam_step(a, cur_stream()), "beam_step");
+}
+
+// out: int64 [B, K, width] with the prompts in place; scores: fp32 [B, K]
+void beam_finalize(const at::Tensor& state, const at::Tensor& score, const at::Tensor& len,
+                   const at::Tensor& tok_trace, const at::Tensor& parent_trace, const at::Tensor& out,
+                   const at::Tensor& scores, int64_t T0, int64_t n_steps, double length_penalty) {
+  check_cuda(out, "out", I64);
+  TORCH_CHECK(out.dim() == 3, "beam_finalize: out must be [B, K, width]");
+  const int64_t B = out.size(0), K = out.size(1), R = B * K;
+  TORCH_CHECK(B >= 1 && K >= 1 && R <= PDE_DS_MAX_ROWS, "beam_finalize: B * K <= ", PDE_DS_MAX_ROWS);
+  check_state(state);
+  check_cuda(score, "score", F32, R);
+  check_cuda(len, "len", I32, R);
+  TORCH_CHECK(tok_trace.dim() == 2 && tok_trace.size(1) == R && n_steps >= 1 && n_steps <= tok_trace.size(0) &&
+                  T0 >= 0 && T0 + n_steps <= out.size(2),
+              "beam_finalize: traces [>= n_steps, R] and out wide enough for T0 + n_steps");
+  check_cuda(tok_trace, "tok_trace", I32, tok_trace.size(0) * R);
+  check_cuda(parent_trace, "parent_trace", I32, tok_trace.size(0) * R);
+  check_cuda(scores, "scores", F32, R);
+  PdeBeamFinal a{};
+  a.state = ptr<int>(state);
+  a.score = ptr<float>(score);
+  a.len = ptr<int>(len);
+  a.tok_trace = ptr<int>(tok_trace);
+  a.parent_trace = ptr<int>(parent_trace);
+  a.out = ptr<int64_t>(out);
+  a.scores = ptr<float>(scores);
+  a.B = (int)B;
+  a.K = (int)K;
+  a.T0 = (int)T0;
+  a.out_stride = (int)out.size(2);
+  a.n_steps = (int)n_steps;
+  a.length_penalty = length_penalty;
+  hip_check(pde_beam_finalize(a, cur_stream()), "beam_finalize");
+}
+
+// cache_fill of the B prompts into rows b * K of a cache layer of B * K rows
+void cache_fill_beam(const at::Tensor& qkv, const at::Tensor& cache, int64_t T0, int64_t H, int64_t K) {
+  TORCH_CHECK(qkv.dim() == 3 && H >= 1 && qkv.size(2) == 3 * H * 64, "cache_fill: qkv must be [B, Tpad, 3 * H * 64]");
+  const int64_t B = qkv.size(0), Tpad = qkv.size(1);
+  TORCH_CHECK(K >= 1 && B * K <= PDE_DS_MAX_ROWS, "cache_fill: B * K <= ", PDE_DS_MAX_ROWS);
+  check_cuda(qkv, "qkv", BF16);
+  check_al16(qkv, "qkv");
+  check_cache(cache, B * K, H);
+  TORCH_CHECK(T0 >= 1 && T0 <= Tpad && T0 <= cache.size(3), "cache_fill: 1 <= T0 <= min(Tpad, Tmax), got ", T0);
+  hip_check(pde_cache_fill_beam(qkv.data_ptr(), cache.data_ptr(), (int)B, (int)K, (int)H, (int)Tpad, (int)T0,
+                                (int)cache.size(3), cur_stream()),
+            "cache_fill");
+}
+
 }  // namespace
 
 void register_decode(pybind11::module& m) {
@@ -267,6 +402,13 @@ void register_decode(pybind11::module& m) {
         py::arg("ban") = py::none(), py::arg("n_ban") = 0, py::arg("stop") = py::none(), py::arg("n_stop") = 0,
         py::arg("stop_hit") = py::none());
   m.def("decode_count_prompt", &count_prompt);
+  m.def("decode_attention_beam", &decode_attention_beam);
+  m.def("beam_step", &beam_step, py::arg("logits"), py::arg("V"), py::arg("K"), py::arg("state"), py::arg("next"),
+        py::arg("score"), py::arg("len"), py::arg("cand_score"), py::arg("cand_tok"), py::arg("table"),
+        py::arg("Tmax"), py::arg("tok_trace"), py::arg("parent_trace"), py::arg("score_trace"),
+        py::arg("logits_out"), py::arg("eos"));
+  m.def("beam_finalize", &beam_finalize);
+  m.def("cache_fill_beam", &cache_fill_beam);
   m.attr("DECODE_STATE_WORDS") = PDE_DS_WORDS;
 }
 

@@ -124,6 +124,68 @@ hipError_t pde_sample_hist(PdeSample a, PdeSampleProc p, PdeSampleHist h, hipStr
 hipError_t pde_count_prompt(const int64_t* idx, const int* state, int* counts, int B, int width, int stride, int T0,
                             int Vp, hipStream_t st);
 
+// ------------------------------------------------------------------------------------------ beam search
+// num_beams = K hypotheses per prompt live in the physical rows r = b * K + k of the R = B * K <= PDE_DS_MAX_ROWS
+// rows the decode step has; the rows of one prompt share its position offset.  The KV cache is never reordered:
+// an ancestor table says which physical row holds each position's K and V of the hypothesis that lives in row r.
+//
+//   anc        bytes [2][PDE_DS_MAX_ROWS][stride], stride >= Tmax and a multiple of 4.  A decode step at the state's
+//              step s reads half s & 1; the beam step at s reads that half and writes the other one:
+//              anc'[b*K + j][t] = anc[b*K + parent_j][t] for t < p_b, and anc'[b*K + j][p_b] = b*K + parent_j (the
+//              parent's own row, where it appended position p_b).  Entries past p_b are never read.
+//   state      words 8..23 are the rows' finished flags, as for the sampler; the draw number does not move.
+typedef struct PdeBeamTable {
+  const unsigned char* anc;
+  int stride;
+} PdeBeamTable;
+// pde_decode_attention with key j < p_b of row b read from cache row anc[b][j]; row p_b is appended to row b
+hipError_t pde_decode_attention_beam(const void* qkv, void* cache, const int* state, float* part, void* out, int B,
+                                     int H, int Tmax, float scale, PdeBeamTable t, hipStream_t st);
+
+// One beam step (definition: ops/decode.py).  Stage 1, a block per row: lse_r and the row's K best logits, lowest
+// index first among equal ones, as (score = S[r] + (x - lse_r), token) pairs in cand_*.  Stage 2, a block per
+// prompt: the K best of the group's candidates by (score descending, parent * V + token ascending) become the new
+// rows; it writes next, S, the finished flags, len, the trace slots of step s and the other half of the table.  A
+// one-thread tail then advances position and step.
+typedef struct PdeBeam {
+  const void* logits;     // [R, Vp] bf16; at step 0 only rows b * K are read
+  int* state;             // PDE_DS_WORDS
+  int64_t* next;          // [R]
+  float* score;           // [R] S
+  int* len;               // [R] generated tokens, the finishing eos included
+  float* cand_score;      // [R, K] workspace
+  int* cand_tok;          // [R, K] workspace
+  unsigned char* anc;     // the table, both halves
+  int* tok_trace;         // [max_new, R]
+  int* parent_trace;      // [max_new, R]
+  float* score_trace;     // [max_new, R]
+  void* logits_out;       // [R, max_new, V] bf16 or null
+  int B, K, V, Vp, Tmax, stride, max_new;
+  int eos;                // -1: none
+} PdeBeam;
+hipError_t pde_beam_step(PdeBeam a, hipStream_t st);
+
+// After the last step: rank the K rows of every prompt by S / len^length_penalty (descending, lower row first on
+// ties; computed in fp64) and write hypothesis of rank i to out[b, i, len_b .. len_b + n_steps) by walking the
+// parents back from its last row, one thread per hypothesis; scores[b, i] = fp32 of its ranking score.
+typedef struct PdeBeamFinal {
+  const int* state;
+  const float* score;
+  const int* len;
+  const int* tok_trace;
+  const int* parent_trace;
+  int64_t* out;           // [B, K, out_stride]
+  float* scores;          // [B, K]
+  int B, K, T0, out_stride, n_steps;
+  double length_penalty;
+} PdeBeamFinal;
+hipError_t pde_beam_finalize(PdeBeamFinal a, hipStream_t st);
+
+// pde_cache_fill for a beam search: prompt b of the prefill c_attn output [B, Tpad, 3 * H * 64] goes to row
+// b * K of a cache of B * K rows
+hipError_t pde_cache_fill_beam(const void* qkv, void* cache, int B, int K, int H, int Tpad, int T0, int Tmax,
+                               hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,15 +143,19 @@ class Block(tnn.Module):
         x, h = T.add_layer_norm_residual(x, a, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps)
         return x, self.mlp(h), qkv
 
-    def decode_deferred(self, x, delta, cache, state):
+    def decode_deferred(self, x, delta, cache, state, beam_table=None):
         """One-token ``forward_deferred`` over the decode kernels: ``x`` / ``delta`` are ``[B, C]``, the
-        new K and V are appended to ``cache`` at the position held by ``state``."""
+        new K and V are appended to ``cache`` at the position held by ``state``.  ``beam_table`` (a beam search's
+        ancestor table) makes the attention read the earlier positions through it."""
         if delta is None:
             x, h = T.layer_norm_residual(x, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
         else:
             x, h = T.add_layer_norm_residual(x, delta, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
         qkv = D.skinny_linear(h, self.attn.c_attn.weight, self.attn.c_attn.bias)
-        a = D.decode_attention(qkv, cache, self.layer_idx, state)
+        if beam_table is None:
+            a = D.decode_attention(qkv, cache, self.layer_idx, state)
+        else:
+            a = D.decode_attention(qkv, cache, self.layer_idx, state, beam_table=beam_table)
         a = D.skinny_linear(a, self.attn.c_proj.weight, self.attn.c_proj.bias)
         x, h = T.add_layer_norm_residual(x, a, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps)
         f = D.skinny_linear(h, self.mlp.c_fc.weight, self.mlp.c_fc.bias, gelu=True)
@@ -274,7 +278,8 @@ class GPT(tnn.Module):
                  eos_token_id=None, use_graph=True, return_logits=False, top_p=None, prompt_lens=None,
                  pad_token_id=0, _after_prefill=None, repetition_penalty=1.0, frequency_penalty=0.0,
                  presence_penalty=0.0, logit_bias=None, suppress_tokens=None, min_new_tokens=0,
-                 no_repeat_ngram_size=0, bad_words_ids=None, stop_sequences=None):
+                 no_repeat_ngram_size=0, bad_words_ids=None, stop_sequences=None, num_beams=1, length_penalty=1.0,
+                 return_beams=False, _beam_trace=None):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` ``[B, T0]`` (``T0 >= 1``).
 
         Returns ``[B, T0 + max_new_tokens]`` int64, and with ``return_logits`` also the logits every token
@@ -321,6 +326,20 @@ class GPT(tnn.Module):
         buffer.  With ``use_graph`` that step is captured once and replayed per token: no host work and no
         host read until the result.  CPU: the plain definition, a full forward per token.
 
+        ``num_beams = K > 1`` runs beam search instead of sampling (definition in ``ops/decode.py``): every prompt
+        keeps ``K`` hypotheses, every step extends them by the ``K`` best of their continuations by cumulative
+        log-probability, a hypothesis that emits ``eos_token_id`` is frozen, and after ``max_new_tokens`` steps they
+        are ranked by ``score / length ** length_penalty``.  The result is the best hypothesis per prompt in the
+        layout above; ``return_beams=True`` returns ``(out [B, K, T0 + max_new_tokens], scores [B, K] fp32)`` in rank
+        order instead, and ``return_logits`` adds the raw logits every physical row ``b * K + k`` saw,
+        ``[B * K, max_new_tokens, V]`` by row and step (step 0 fills row ``b * K`` only).  It is deterministic: no
+        random number is drawn and ``generator`` is not touched.  The sampling keywords, the processors and the
+        history constraints must stay at their defaults with it (``ValueError``).  On the GPU ``B * K <= 16``; the
+        prompt is prefilled once per prompt, the KV cache is never reordered -- the decode attention reads it
+        through a small per-row ancestor table that the selection kernels rewrite -- and the selection runs on the
+        device, so the step still replays as one graph.  With ``num_beams=1`` nothing changes and nothing is
+        allocated.
+
         ``T0 + max_new_tokens`` (``max(prompt_lens) + max_new_tokens`` for a ragged batch) must not exceed
         ``block_size`` (learned absolute positions: no sliding window)."""
         cfg = self.config
@@ -332,6 +351,26 @@ class GPT(tnn.Module):
         if not 0 <= int(pad_token_id) < cfg.vocab_size:
             raise ValueError("generate: pad_token_id must be a token of the vocabulary")
         dev = self.transformer.wte.weight.device
+        # num_beams and length_penalty are checked for every call; eos_token_id only where beam search runs, so the
+        # sampling path keeps validating it where and as it did
+        beam = D.BeamConfig(num_beams, length_penalty, who="generate")
+        if return_beams and not beam.active:
+            raise ValueError("generate: return_beams needs num_beams > 1")
+        if beam.active:
+            beam = D.BeamConfig(num_beams, length_penalty, eos_token_id, who="generate")
+            given = dict(temperature=temperature != 1.0, top_k=top_k is not None, top_p=top_p is not None,
+                         seed=seed is not None, generator=generator is not None,
+                         repetition_penalty=repetition_penalty != 1.0, frequency_penalty=frequency_penalty != 0.0,
+                         presence_penalty=presence_penalty != 0.0, logit_bias=logit_bias is not None,
+                         suppress_tokens=suppress_tokens is not None, min_new_tokens=min_new_tokens != 0,
+                         no_repeat_ngram_size=no_repeat_ngram_size != 0, bad_words_ids=bad_words_ids is not None,
+                         stop_sequences=stop_sequences is not None)
+            off = [name for name, on in given.items() if on]
+            if off:
+                raise ValueError(f"generate: num_beams > 1 does not combine with {', '.join(off)} (beam search is "
+                                 "deterministic and takes no processors or constraints)")
+            return self._generate_beam(idx.to(dev).long(), max_new_tokens, beam, prompt_lens, int(pad_token_id),
+                                       return_logits, return_beams, use_graph, _after_prefill, _beam_trace)
         config = D.SamplerConfig(
             temperature, top_k, top_p, eos_token_id,
             D.LogitProcessors(repetition_penalty, frequency_penalty, presence_penalty, logit_bias, suppress_tokens,
@@ -355,6 +394,90 @@ class GPT(tnn.Module):
                 return self._generate_cpu(*args)
         finally:
             self.train(was_training)
+
+    def _generate_beam(self, idx, n_new, beam, lens, pad, return_logits, return_beams, use_graph, _after_prefill,
+                       trace):
+        """``generate`` with ``num_beams > 1`` on either device.  ``trace`` (a dict, for tests) receives what every
+        step chose -- ``tok``, ``parent``, ``score`` (``[n_new, B * K]``; on the CPU also ``gap``, ``[n_new, B]``, of
+        ``beam_step_reference``) -- and the rows' final ``S``, ``len`` and ``finished``."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                if idx.is_cuda:
+                    out, scores, logits, tr = self._generate_beam_gpu(idx, n_new, beam, lens, pad, return_logits,
+                                                                      use_graph, _after_prefill)
+                else:
+                    out, scores, logits, tr = self._generate_beam_cpu(idx, n_new, beam, lens, pad, return_logits)
+        finally:
+            self.train(was_training)
+        if trace is not None:
+            trace.update(tr)
+        res = (out, scores) if return_beams else (out[:, 0].contiguous(),)
+        res = res + (logits,) if return_logits else res
+        return res if len(res) > 1 else res[0]
+
+    def _generate_beam_cpu(self, idx, n_new, beam, lens, pad, return_logits):
+        """The plain definition: ``B * K`` hypotheses, a full forward per token, ``beam_step_reference``'s rule.  The
+        hypotheses are reordered physically, so row ``b * K + j`` always holds beam ``j``'s tokens."""
+        V, K = self.config.vocab_size, beam.num_beams
+        B, Tin = idx.shape
+        lens, Tl = _prompt_window(self.config, idx, n_new, lens, beam)
+        R = B * K
+        ln = torch.tensor(lens or [Tin] * B, dtype=torch.int64).repeat_interleave(K)
+        rows, grp = torch.arange(R), (torch.arange(B) * K)[:, None]
+        prompts = D._prompt_out(idx, lens, n_new, pad, "cpu")
+        seq = torch.zeros(R, Tl + n_new, dtype=torch.int64)        # what the model sees: pad columns hold token 0
+        seq[:, :Tl] = torch.where(torch.arange(Tl)[None, :] < ln[:, None], idx[:, :Tl].repeat_interleave(K, 0), 0)
+        S, fin, length = torch.zeros(R, dtype=torch.float64), torch.zeros(R, dtype=torch.bool), torch.zeros(
+            R, dtype=torch.int64)
+        tr = {k: [] for k in ("tok", "parent", "score", "gap")}
+        logits_out = None
+        for s in range(n_new):
+            logits = self(seq[:, :Tl + s])[rows, ln + s - 1]
+            if return_logits:
+                if logits_out is None:
+                    logits_out = torch.zeros(R, n_new, V, dtype=logits.dtype)
+                logits_out[:, s] = logits[:, :V]
+                if s == 0:
+                    logits_out[(rows % K) != 0, 0] = 0
+            parent, tok, score, info = D.beam_step_reference(logits, V, K, S, fin, beam.eos_token_id, first=s == 0,
+                                                             return_info=True)
+            src, tok = (grp + parent).reshape(R), tok.reshape(R)
+            seq = seq[src]
+            seq[rows, ln + s] = tok
+            length = length[src] + (~fin[src]).long()
+            fin = fin[src] | (tok == beam._eos)
+            S = score.reshape(R)
+            for k, v in (("tok", tok), ("parent", parent.reshape(R)), ("score", S), ("gap", torch.from_numpy(info["gap"]))):
+                tr[k].append(v.clone())
+        order, ranked = D.beam_rank_reference(S, length, K, beam.length_penalty)
+        out = prompts[:, None, :].repeat(1, K, 1)
+        for b in range(B):
+            for i in range(K):
+                r, n = b * K + int(order[b, i]), int(ln[b * K])
+                out[b, i, n:n + n_new] = seq[r, n:n + n_new]
+        tr = {k: torch.stack(v) for k, v in tr.items()}
+        tr.update(S=S, len=length, finished=fin)
+        return out, ranked.float(), logits_out, tr
+
+    def _generate_beam_gpu(self, idx, n_new, beam, lens, pad, return_logits, use_graph, _after_prefill):
+        ses = DecodeSession(self, idx, n_new, return_logits=return_logits, prompt_lens=lens, pad_token_id=pad, beam=beam)
+        if _after_prefill is not None:
+            _after_prefill(ses.cache)
+        if n_new > 1 and use_graph:
+            graph = ses.capture()
+            for _ in range(n_new - 1):
+                graph.replay()
+        else:
+            for _ in range(n_new - 1):
+                ses.step()
+        bb = ses.beam
+        out, scores = bb.finalize()
+        R = bb.B * bb.K
+        tr = dict(tok=bb.tok, parent=bb.parent, score=bb.score_trace, S=bb.score, len=bb.len,
+                  finished=bb.state.finished[:R])
+        return out, scores, bb.logits_out, tr
 
     def _generate_cpu(self, idx, n_new, config, generator, lens, pad, return_logits):
         """One right-padded forward per token; row ``b``'s logits are row ``len_b + s - 1`` of it (causal:
@@ -452,17 +575,26 @@ class DecodeSession:
     included.  When none is on, ``history`` and ``stop_hit`` stay ``None``.
 
     ``config`` (an ``ops.SamplerConfig``, as ``GPT.generate`` passes) stands for all the sampling keywords.  The
-    buffers named above live in ``buffers``, an ``ops.SampleBuffers``, and are mirrored as attributes."""
+    buffers named above live in ``buffers``, an ``ops.SampleBuffers``, and are mirrored as attributes.
+
+    ``beam`` (an ``ops.BeamConfig`` with ``num_beams = K > 1``) makes it a beam search over ``B * K <= 16`` physical rows:
+    the prefill still runs ``B`` rows and stores each prompt's K and V once, ``buffers`` is an ``ops.BeamBuffers`` (also
+    ``beam``; ``None`` otherwise), every step's attention reads the cache through its ancestor table and the beam
+    selection takes the sampler's place.  ``beam.finalize()`` ranks the hypotheses after the last step."""
 
     def __init__(self, model, idx, n_new, temperature=1.0, top_k=None, rng_state=None, eos=None,
                  return_logits=False, top_p=None, prompt_lens=None, pad_token_id=0, processors=None,
                  repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None,
                  suppress_tokens=None, min_new_tokens=0, history=None, no_repeat_ngram_size=0, bad_words_ids=None,
-                 stop_sequences=None, config=None):
+                 stop_sequences=None, config=None, beam=None):
         cfg, t = model.config, model.transformer
         dev = idx.device
         B = idx.shape[0]
-        if config is None:
+        beam = beam if beam is not None and beam.active else None
+        K = 1 if beam is None else beam.num_beams
+        if beam is not None:
+            config = beam               # the sampler's settings play no part; `check` has the same signature
+        elif config is None:
             if processors is None:
                 processors = D.LogitProcessors(repetition_penalty, frequency_penalty, presence_penalty, logit_bias,
                                                suppress_tokens, min_new_tokens, eos)
@@ -471,8 +603,9 @@ class DecodeSession:
             config = D.SamplerConfig(temperature, top_k, top_p, eos, processors, history, who="generate")
         lens, T0 = _prompt_window(cfg, idx, n_new, prompt_lens, config)
         wte, wpe = t.wte.weight, t.wpe.weight
-        if B > D.MAX_ROWS:
-            raise NotImplementedError(f"generate: at most {D.MAX_ROWS} sequences on the GPU (got {B})")
+        if B * K > D.MAX_ROWS:
+            raise NotImplementedError(f"generate: at most {D.MAX_ROWS} sequences on the GPU (got {B}"
+                                      + (f" x {K} beams)" if K > 1 else ")"))
         if wte.dtype != torch.bfloat16:
             raise NotImplementedError("generate: the GPU path is bf16")
         Tpad = min(-(-T0 // 128) * 128, cfg.block_size)
@@ -481,7 +614,7 @@ class DecodeSession:
                                       f"(block_size {cfg.block_size} caps it at {Tpad})")
         self.model, self.T0, self.V = model, T0, cfg.vocab_size
         # prefill: the training kernels over the padded prompt (causal: the pad never reaches positions < T0)
-        self.cache = D.KVCache(cfg, B, T0 + n_new, dev)
+        self.cache = D.KVCache(cfg, B * K, T0 + n_new, dev)
         idx_pad = torch.zeros(B, Tpad, device=dev, dtype=torch.int64)
         if lens is None:
             idx_pad[:, :T0] = idx
@@ -495,7 +628,10 @@ class DecodeSession:
             # ragged: the cache rows len_b .. T0 - 1 of a shorter row come from pad columns here; each is
             # overwritten by the decode step that first reaches it (the append at p_b) before any read,
             # since a step at p_b reads rows <= p_b only
-            D.cache_fill(qkv, self.cache, l, T0)
+            if beam is None:
+                D.cache_fill(qkv, self.cache, l, T0)
+            else:                                # once per prompt, into the group's first row
+                D.cache_fill(qkv, self.cache, l, T0, num_beams=K)
         # only the last prompt row goes through ln_f and the LM head: the [B * Tpad, Vp] logits are never formed
         if lens is None:
             xl, dl = x[:, T0 - 1].contiguous(), delta[:, T0 - 1].contiguous()
@@ -505,6 +641,19 @@ class DecodeSession:
         h = T.add_layer_norm_residual(xl, dl, t.ln_f.weight, t.ln_f.bias, t.ln_f.eps)[1]
         # state, next, out and logits_out; with processors or constraints on also counts (the prompt flags set), work,
         # bias and stop_hit, which stay None otherwise: the sampler is then called exactly as without them
+        self.beam = self._table = None
+        if beam is not None:
+            # the B * K rows' state, scores, lengths, ancestor table and traces; the prompt's logits go to row b * K,
+            # the only one the first beam step reads
+            self.buffers = self.beam = b = D.BeamBuffers(beam, idx, lens, n_new, self.V, wte.shape[0], dev,
+                                                         self.cache.max_len, pad_token_id, return_logits)
+            self._table = b.table
+            self.processors = self.history = self.counts = self.work = self.bias = self.stop_hit = None
+            self.state, self.next, self.out, self.logits_out = b.state, b.next, b.out, b.logits_out
+            logits = torch.zeros(B * K, wte.shape[0], device=dev, dtype=wte.dtype)
+            logits[::K] = D.skinny_linear(h, wte)
+            self._sample(logits)
+            return
         self.buffers = b = D.SampleBuffers(config, idx, lens, n_new, self.V, wte.shape[0], dev, rng_state, pad_token_id,
                                            return_logits)
         self.processors, self.history = config.processors, config.history
@@ -520,7 +669,7 @@ class DecodeSession:
         t = self.model.transformer
         x, delta = D.decode_embed(self.next, t.wte.weight, t.wpe.weight, self.state), None
         for blk in t.h:
-            x, delta = blk.decode_deferred(x, delta, self.cache, self.state)
+            x, delta = blk.decode_deferred(x, delta, self.cache, self.state, self._table)
         h = T.add_layer_norm_residual(x, delta, t.ln_f.weight, t.ln_f.bias, t.ln_f.eps)[1]
         self._sample(D.skinny_linear(h, t.wte.weight))
 

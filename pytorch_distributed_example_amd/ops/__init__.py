@@ -14,6 +14,8 @@ from .transformer import LossTargets, doc_bounds, loss_targets  # noqa: F401
 from . import rng  # noqa: F401
 from .rng import DeviceRNG, dropout_mask, effective_p  # noqa: F401
 from . import decode  # noqa: F401
+from .decode import (BeamBuffers, BeamConfig, beam_rank_reference, beam_step, beam_step_reference,  # noqa: F401
+                     beam_table)
 from .decode import (DecodeState, HistoryConstraints, KVCache, LogitProcessors, SampleBuffers,  # noqa: F401
                      SamplerConfig, TokenCounts, check_top_p, decode_attention, decode_embed, history_bans_reference,
                      key16_to_float, process_logits_reference, sample, sample_reference, skinny_linear)

@@ -75,6 +75,29 @@ a finished row included:
    not delay a stop.  ``stop_hit[b]`` (int32) is ``-1``, or the lowest index in list order of a sequence that
    matched when the row finished.
 
+Beam search (``BeamConfig``; ``beam_step`` on the GPU, ``beam_step_reference`` in numpy fp64).  ``num_beams = K``,
+prompts ``b = 0 .. B-1``, physical rows ``r = b * K + k``, ``R = B * K``.  Row ``r`` carries ``S[r]`` (cumulative
+log-probability, fp32 on the device), ``fin[r]`` and ``len[r]`` (generated tokens, the eos that finished it
+included).  It is deterministic and draws no random number.  At step ``s`` (0 = first generated token) the
+candidates of group ``b`` are::
+
+    row r live:      cand(k, v) = S[r] + (x_v - lse_r)  for every v < V,  x_v = float(logits[r, v]),
+                     lse_r = logsumexp(x[:V])
+    row r finished:  one candidate, cand(k, eos) = S[r]   (frozen: it keeps emitting eos, its score stands)
+    step 0:          only k = 0 exists (the prompt's logits, S = 0); needs V >= K
+
+The new beams ``j = 0 .. K-1`` are the ``K`` largest candidates in descending order, the lower flat index
+``k * V + v`` first among equal scores.  Beam ``j`` from candidate ``(k, v)``: ``parent[s][b*K+j] = k``,
+``tok[s][b*K+j] = v``, ``S' = cand``, ``fin' = fin[k] or v == eos``, ``len' = len[k] + (0 if fin[k] else 1)``.  Without
+an eos no beam finishes.  Every step runs; finished beams are frozen, so stopping early would change nothing.  The
+final ranking is by ``S / len ** length_penalty`` descending, the lower beam first on ties, and a hypothesis is
+recovered by walking ``parent`` backwards from its last row.
+
+The KV cache is never reordered for it.  ``beam_table`` is a per-row ancestor table -- which physical row holds each
+position's K and V of the hypothesis living in row ``r`` -- that ``decode_attention(beam_table=)`` reads through and
+the beam step rewrites into its other half (``PdeBeamTable`` in ``pde_decode.h``); the prompt's K and V are stored
+once per prompt (``cache_fill(num_beams=)``).
+
 GPU tensors always run the framework kernels; an unsupported shape raises ``NotImplementedError``.
 """
 from __future__ import annotations
@@ -234,30 +257,43 @@ class KVCache:
         return self._part
 
 
-def cache_fill(qkv, cache: KVCache, layer: int, T0: int):
-    """K and V of positions ``0 .. T0-1`` of a prefill c_attn output ``[B, Tpad, 3C]`` -> the layer's cache."""
+def cache_fill(qkv, cache: KVCache, layer: int, T0: int, num_beams: int = 1):
+    """K and V of positions ``0 .. T0-1`` of a prefill c_attn output ``[B, Tpad, 3C]`` -> the layer's cache.  With
+    ``num_beams = K > 1`` the cache holds ``B * K`` rows and prompt ``b`` goes to row ``b * K``, the one the initial
+    ancestor table of a beam search (``beam_table``) points the whole group at."""
     B, Tp, C3 = qkv.shape
-    H = cache.n_head
-    if C3 != 3 * H * 64 or B != cache.batch or not 1 <= T0 <= min(Tp, cache.max_len):
+    H, K = cache.n_head, int(num_beams)
+    if C3 != 3 * H * 64 or K < 1 or B * K != cache.batch or not 1 <= T0 <= min(Tp, cache.max_len):
         raise ValueError(f"cache_fill: qkv {tuple(qkv.shape)} does not fit the cache / T0 = {T0}")
     if qkv.is_cuda:
         if qkv.dtype != _BF16:
             raise NotImplementedError("cache_fill: the GPU path is bf16")
-        kernels().cache_fill(qkv if qkv.is_contiguous() else qkv.contiguous(), cache.layer(layer), int(T0), H)
+        qkv = qkv if qkv.is_contiguous() else qkv.contiguous()
+        if K > 1:
+            if B * K > MAX_ROWS:
+                raise NotImplementedError(f"cache_fill: B * num_beams <= {MAX_ROWS} rows on the GPU (got {B * K})")
+            kernels().cache_fill_beam(qkv, cache.layer(layer), int(T0), H, K)
+        else:
+            kernels().cache_fill(qkv, cache.layer(layer), int(T0), H)
         return
     C = C3 // 3
     for s in range(2):
         kv = qkv[:, :T0, (1 + s) * C:(2 + s) * C].reshape(B, T0, H, 64).transpose(1, 2)
-        cache.data[layer, s, :, :, :T0] = kv
+        cache.data[layer, s, ::K, :, :T0] = kv
 
 
-def decode_attention(qkv_row, cache: KVCache, layer: int, state: DecodeState):
+def decode_attention(qkv_row, cache: KVCache, layer: int, state: DecodeState, beam_table=None):
     """One decode step of causal attention: append the new token's K and V (from its c_attn row
     ``[B, 3C]``) at the state's position ``p`` and return ``softmax(q K[0..p]^T / 8) V[0..p]`` as
     ``[B, C]``.  Fixed 128-key chunks with fp32 partials combined in chunk order: the output for a given
     ``p`` is bit-identical across runs and independent of the cache length.  ``p`` is per row, ``p_b`` = the
     state's position plus row ``b``'s offset, and a row's output depends on its own ``p_b`` only: it is
-    bit-identical to a call in which every row is at ``p_b``."""
+    bit-identical to a call in which every row is at ``p_b``.
+
+    ``beam_table`` (uint8 ``[2, 16, stride >= max_len]``, see ``beam_table()``) is a beam search's ancestor table:
+    key and value ``j < p_b`` of row ``b`` are read from cache row ``table[step & 1, b, j]``, with ``step`` the state's;
+    position ``p_b`` is still appended to row ``b`` itself.  The arithmetic is the same, so the output is
+    bit-identical to the call without a table on a cache gathered through it."""
     B, C3 = qkv_row.shape
     H = cache.n_head
     if C3 != 3 * H * 64 or B != cache.batch:
@@ -270,15 +306,24 @@ def decode_attention(qkv_row, cache: KVCache, layer: int, state: DecodeState):
         if B > MAX_ROWS:
             raise NotImplementedError(f"decode_attention: at most {MAX_ROWS} rows on the GPU (got {B})")
         out = torch.empty(B, C, device=qkv_row.device, dtype=_BF16)
-        kernels().decode_attention(qkv_row if qkv_row.is_contiguous() else qkv_row.contiguous(), cache.layer(layer),
-                                   state.buf, cache.partials(), out, H, scale)
+        qkv_row = qkv_row if qkv_row.is_contiguous() else qkv_row.contiguous()
+        if beam_table is None:
+            kernels().decode_attention(qkv_row, cache.layer(layer), state.buf, cache.partials(), out, H, scale)
+        else:
+            kernels().decode_attention_beam(qkv_row, cache.layer(layer), state.buf, cache.partials(), out, H, scale,
+                                            beam_table)
         return out
     q, k, v = (t.reshape(B, H, 64) for t in qkv_row.split(C, dim=1))
     rows = []
+    anc = None if beam_table is None else beam_table[state.step() & 1].long()
     for b, p in enumerate(state.row_pos(B)):
         cache.data[layer, 0, b, :, p] = k[b]
         cache.data[layer, 1, b, :, p] = v[b]
-        Kc, Vc = cache.data[layer, 0, b, :, :p + 1].float(), cache.data[layer, 1, b, :, :p + 1].float()
+        if anc is None:
+            Kc, Vc = cache.data[layer, 0, b, :, :p + 1].float(), cache.data[layer, 1, b, :, :p + 1].float()
+        else:       # positions < p through the table ([p, H, 64] -> [H, p, 64]), position p from the row itself
+            src, t = torch.cat([anc[b, :p], torch.tensor([b])]), torch.arange(p + 1)
+            Kc, Vc = (cache.data[layer, s][src, :, t].transpose(0, 1).float() for s in (0, 1))
         s = torch.einsum("hd,htd->ht", q[b].float(), Kc) * scale
         rows.append(torch.einsum("ht,htd->hd", torch.softmax(s, -1), Vc).reshape(C))
     return torch.stack(rows).to(qkv_row.dtype)
@@ -936,13 +981,7 @@ class SampleBuffers:
         self.state = DecodeState(dev, rng_state, pos=T0 - 1 if pos is None else pos, step=0,
                                  row_offsets=None if lens is None else [n - T0 for n in lens],
                                  rows=MAX_ROWS if dev.type == "cuda" else max(B, MAX_ROWS))
-        if lens is None:
-            self.out = torch.zeros(B, T0 + n_new, device=dev, dtype=torch.int64)
-            self.out[:, :T0] = idx
-        else:
-            real = torch.arange(Tin, device=dev)[None, :] < torch.tensor(lens, device=dev)[:, None]
-            self.out = torch.full((B, Tin + n_new), int(pad_token_id), device=dev, dtype=torch.int64)
-            self.out[:, :Tin] = torch.where(real, idx, self.out[:, :Tin])
+        self.out = _prompt_out(idx, lens, n_new, pad_token_id, dev)
         self.next = torch.zeros(B, device=dev, dtype=torch.int64)
         self.logits_out = torch.empty(B, n_new, self.V, device=dev, dtype=dtype) if return_logits else None
         self.counts = self.work = self.bias = self.stop_hit = None
@@ -970,3 +1009,196 @@ class SampleBuffers:
     def restore(self, saved):
         for t, s in zip(self._dirty(), saved):
             t.copy_(s)
+
+
+# --------------------------------------------------------------------------------------- beam search
+def _prompt_out(idx, lens, n_new, pad_token_id, device):
+    """The output rows of a generation before its first token: ``[B, Tin + n_new]`` int64 with the prompts in place,
+    zeros after them for a batch of one length, ``pad_token_id`` everywhere else for a ragged one."""
+    B, Tin = idx.shape
+    if lens is None:
+        out = torch.zeros(B, Tin + n_new, device=device, dtype=torch.int64)
+        out[:, :Tin] = idx
+        return out
+    real = torch.arange(Tin, device=device)[None, :] < torch.tensor(lens, device=device)[:, None]
+    out = torch.full((B, Tin + n_new), int(pad_token_id), device=device, dtype=torch.int64)
+    out[:, :Tin] = torch.where(real, idx.to(device), out[:, :Tin])
+    return out
+
+
+def beam_step_reference(logits, V: int, num_beams: int, scores, finished, eos_token_id=None, first: bool = False,
+                        return_info: bool = False):
+    """One beam step (module docstring) in numpy fp64.  ``logits`` is ``[R, Vp]`` with ``R = B * num_beams`` (any
+    float dtype; columns ``>= V`` never participate), ``scores`` the ``R`` cumulative log-probabilities, ``finished``
+    the ``R`` flags, ``first`` says that this is step 0, where only beam 0 of every group exists.  Returns
+    ``(parent, tok, score)``, each ``[B, num_beams]`` (int64, int64, fp64) in the order of the new beams.
+
+    With ``return_info`` also a dict: ``best``, the ``num_beams + 1`` best candidate scores per group (``-inf`` where
+    the group has fewer candidates), and ``gap``, per group the smallest difference between consecutive entries of
+    that list -- how far the selection and its order are from changing.  Two candidates of one row with equal logits
+    differ by index on either side: that pair counts as ``inf``."""
+    K = int(num_beams)
+    if logits.dim() != 2 or K < 1 or logits.shape[0] % K or not K <= V <= logits.shape[1]:
+        raise ValueError("beam_step_reference: logits [B * num_beams, Vp] with num_beams <= V <= Vp")
+    R = logits.shape[0]
+    B = R // K
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    lg = logits.detach().float().cpu().numpy().astype(np.float64)[:, :V]
+    S = np.asarray(torch.as_tensor(scores).detach().cpu().numpy(), dtype=np.float64).reshape(R)
+    fin = np.asarray(torch.as_tensor(finished).detach().cpu().numpy()).astype(bool).reshape(R) & (eos >= 0)
+    mx = lg.max(axis=1)
+    lse = mx + np.log(np.exp(lg - mx[:, None]).sum(axis=1))
+    n = min(K + 1, V)
+    top = np.argsort(-lg, axis=1, kind="stable")[:, :n]          # equal logits: lowest index first
+    parent, tok, score = (np.zeros((B, K), dtype=t) for t in (np.int64, np.int64, np.float64))
+    best = np.full((B, K + 1), -np.inf)
+    gap = np.full(B, np.inf)
+    for b in range(B):
+        cand = []                                                # (-score, flat index, k, v, logit or None)
+        for k in range(1 if first else K):
+            r = b * K + k
+            if fin[r]:
+                cand.append((-S[r], k * V + eos, k, eos, None))
+            else:
+                cand += [(-(S[r] + (lg[r, v] - lse[r])), k * V + int(v), k, int(v), lg[r, v]) for v in top[r]]
+        cand.sort(key=lambda c: c[:2])
+        if len(cand) < K:
+            raise ValueError("beam_step_reference: fewer candidates than beams")
+        for j, c in enumerate(cand[:K]):
+            parent[b, j], tok[b, j], score[b, j] = c[2], c[3], -c[0]
+        for j, c in enumerate(cand[:K + 1]):
+            best[b, j] = -c[0]
+            if j > 0:
+                a = cand[j - 1]
+                same = a[2] == c[2] and a[4] is not None and a[4] == c[4]
+                if not same:
+                    gap[b] = min(gap[b], c[0] - a[0])
+    res = tuple(torch.from_numpy(x) for x in (parent, tok, score))
+    return (*res, {"best": best, "gap": gap}) if return_info else res
+
+
+def beam_rank_reference(scores, lengths, num_beams: int, length_penalty: float = 1.0):
+    """The final ranking in numpy fp64: ``(order, ranked)``, each ``[B, num_beams]``; ``order[b, i]`` is the beam of
+    rank ``i`` by ``S / len ** length_penalty`` descending, lower beam first on ties, ``ranked[b, i]`` its score."""
+    K = int(num_beams)
+    S = np.asarray(torch.as_tensor(scores).detach().cpu().numpy(), dtype=np.float64).reshape(-1, K)
+    ln = np.asarray(torch.as_tensor(lengths).detach().cpu().numpy(), dtype=np.float64).reshape(-1, K)
+    fs = S / ln ** float(length_penalty)
+    order = np.argsort(-fs, axis=1, kind="stable")
+    return torch.from_numpy(order), torch.from_numpy(np.take_along_axis(fs, order, axis=1))
+
+
+class BeamConfig:
+    """The settings of a beam search -- ``num_beams``, ``length_penalty``, ``eos_token_id`` -- validated once
+    (``ValueError``).  ``active`` is False for ``num_beams == 1``: the generation then samples as without it."""
+
+    def __init__(self, num_beams: int = 1, length_penalty: float = 1.0, eos_token_id=None, who: str = "beam search"):
+        K = num_beams
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+            raise ValueError(f"{who}: num_beams must be an integer >= 1 (got {K!r})")
+        if not math.isfinite(float(length_penalty)):
+            raise ValueError(f"{who}: length_penalty must be finite (got {length_penalty})")
+        self.num_beams, self.length_penalty = int(K), float(length_penalty)
+        self.eos_token_id = None if eos_token_id is None else _token_id(eos_token_id, f"{who}: eos_token_id")
+        self._eos = -1 if self.eos_token_id is None else self.eos_token_id
+
+    @property
+    def active(self) -> bool:
+        return self.num_beams > 1
+
+    def check(self, B: int, V: int, device=None):
+        """The checks that need the vocabulary: ``num_beams <= V`` (step 0 takes that many tokens of one row) and
+        ``eos_token_id < V``."""
+        if self.num_beams > V:
+            raise ValueError(f"beam search: num_beams = {self.num_beams} exceeds the vocabulary ({V})")
+        if self.eos_token_id is not None and self.eos_token_id >= V:
+            raise ValueError("eos_token_id must be a token of the vocabulary")
+        return self
+
+
+def beam_table(B: int, num_beams: int, max_len: int, device=None):
+    """The ancestor table of a beam search before its first step: uint8 ``[2, 16, stride]`` (``stride``: ``max_len``
+    rounded up to a multiple of 16), entry ``[h, r, t]`` = the physical row that holds position ``t`` of the
+    hypothesis living in row ``r``.  Both halves start at the group's first row ``(r // K) * K``, where the prefill
+    stores the prompt's K and V once.  Layout and update rule: ``PdeBeamTable`` in ``pde_decode.h``."""
+    K, R = int(num_beams), int(B) * int(num_beams)
+    if R > MAX_ROWS:
+        raise NotImplementedError(f"beam search: B * num_beams <= {MAX_ROWS} rows (got {R})")
+    first = (torch.arange(MAX_ROWS) // K * K).clamp(max=max(R - 1, 0)).to(torch.uint8)
+    stride = -(-int(max_len) // 16) * 16
+    return first[None, :, None].repeat(2, 1, stride).contiguous().to(torch.device("cpu" if device is None else device))
+
+
+class BeamBuffers:
+    """What a GPU beam search of ``n_new`` tokens after the prompts ``idx`` (``[B, Tin]``; ``lens`` as for
+    ``SampleBuffers``) keeps between its steps, all on the device, for the ``R = B * num_beams`` physical rows
+    ``r = b * K + k``: the ``DecodeState`` (every row of a group carries the group's offset; the finished flags are the
+    rows'), ``next`` (``[R]``), ``score`` (``S``, fp32 ``[R]``), ``len`` (int32 ``[R]``), the ancestor ``table`` for a
+    cache of ``max_len`` positions, the traces ``tok`` / ``parent`` / ``score_trace`` (``[n_new, R]``: what every step
+    chose), the selection's workspaces and ``logits_out`` (``[R, n_new, V]`` with ``return_logits``).  ``sample(logits)``
+    is one beam step; ``finalize()`` ranks the rows and returns ``(out [B, K, Tin + n_new], scores [B, K])``."""
+
+    def __init__(self, config: BeamConfig, idx, lens, n_new, V, Vp, device, max_len, pad_token_id=0,
+                 return_logits=False, pos=None):
+        dev = torch.device(device)
+        B, Tin = idx.shape
+        K = config.num_beams
+        R = B * K
+        if R > MAX_ROWS:
+            raise NotImplementedError(f"beam search: B * num_beams <= {MAX_ROWS} rows on the GPU (got {B} * {K})")
+        config.check(B, V)
+        self.config, self.V, self.B, self.K, self.n_new, self.max_len = config, int(V), B, K, int(n_new), int(max_len)
+        self.T0 = T0 = Tin if lens is None else max(lens)
+        offs = None if lens is None else [n - T0 for n in lens for _ in range(K)]
+        self.state = DecodeState(dev, None, pos=T0 - 1 if pos is None else pos, step=0, row_offsets=offs)
+        self.next = torch.zeros(R, device=dev, dtype=torch.int64)
+        self.score = torch.zeros(R, device=dev, dtype=torch.float32)
+        self.len = torch.zeros(R, device=dev, dtype=torch.int32)
+        self.table = beam_table(B, K, max_len, dev)
+        self.tok = torch.zeros(n_new, R, device=dev, dtype=torch.int32)
+        self.parent = torch.zeros(n_new, R, device=dev, dtype=torch.int32)
+        self.score_trace = torch.zeros(n_new, R, device=dev, dtype=torch.float32)
+        self._cand = (torch.zeros(R, K, device=dev, dtype=torch.float32), torch.zeros(R, K, device=dev, dtype=torch.int32))
+        self.logits_out = torch.zeros(R, n_new, self.V, device=dev, dtype=_BF16) if return_logits else None
+        self.out = _prompt_out(idx, lens, n_new, pad_token_id, dev)[:, None, :].repeat(1, K, 1).contiguous()
+        self.scores = torch.zeros(B, K, device=dev, dtype=torch.float32)
+
+    def sample(self, logits):
+        """One beam step from the ``[R, Vp]`` logits of the rows' current positions; returns ``next``."""
+        return beam_step(logits, self)
+
+    def finalize(self, n_steps=None):
+        """To be called after the last step (``n_steps`` of them, default ``n_new``; nothing is read on the host)."""
+        n = self.n_new if n_steps is None else int(n_steps)
+        kernels().beam_finalize(self.state.buf, self.score, self.len, self.tok, self.parent, self.out, self.scores,
+                                self.T0, n, self.config.length_penalty)
+        return self.out, self.scores
+
+    def _dirty(self):
+        return [self.state.buf, self.next, self.score, self.len]
+
+    def snapshot(self):
+        """Copies of what a step changes besides the trace slots and the table half it writes: state (position, step,
+        finished flags), ``next``, ``S`` and ``len``."""
+        return [t.clone() for t in self._dirty()]
+
+    def restore(self, saved):
+        for t, s in zip(self._dirty(), saved):
+            t.copy_(s)
+
+
+def beam_step(logits, buffers: BeamBuffers):
+    """One beam step on the device (definition in the module docstring; ``beam_step_reference`` is its fp64 twin):
+    a block per row finds ``lse`` and the row's ``K`` best logits, a block per prompt merges the group's candidates
+    and writes ``next``, ``S``, ``len``, the finished flags, the trace slots of the state's step and the other half
+    of the ancestor table, and a one-thread tail advances position and step.  Returns ``next``."""
+    b = buffers
+    if not logits.is_cuda:
+        raise NotImplementedError("beam_step: the device step runs on the GPU; the CPU definition is "
+                                  "beam_step_reference")
+    if logits.dim() != 2 or logits.dtype != _BF16 or logits.shape[1] % 8 or not logits.is_contiguous() \
+            or logits.shape[0] != b.B * b.K:
+        raise NotImplementedError("beam_step: contiguous bf16 logits [B * num_beams, Vp] with Vp % 8 == 0")
+    kernels().beam_step(logits, b.V, b.K, b.state.buf, b.next, b.score, b.len, b._cand[0], b._cand[1], b.table,
+                        b.max_len, b.tok, b.parent, b.score_trace, b.logits_out, b.config._eos)
+    return b.next

@@ -25,10 +25,15 @@ a ``[V]`` logit bias), and under ``--sampler-reps`` the sampler launch with them
 ``--history`` adds a row with the history constraints on (``no_repeat_ngram_size`` 3 and two stop sequences that
 never match, so every row stays live and is scanned at every step; on top of the penalties under ``--penalties``),
 and under ``--sampler-reps`` the sampler launch with them (the ``HIST`` instantiation) on a 512-token history.
+``--beams K`` adds a row with beam search: ``--batch-sizes`` then counts physical rows ``R`` (a multiple of ``K``), the
+plain row runs ``R`` sampled sequences and the beam row ``R / K`` prompts with ``K`` beams each -- the same number of
+rows through the same step, with the table-indirect attention and the beam selection in place of the plain attention
+and the sampler -- and under ``--sampler-reps`` the beam step's three launches alone, on ``randn * 3`` logits and on rows whose logits
+are all equal (every candidate a tie at the threshold: the selection's worst case).
 
     python tools/gpt2_decode_bench.py [--context 512] [--window 64] [--rounds 5] [--batch-sizes 1 16]
                                       [--top-k 50] [--top-p P] [--ragged] [--sampler-reps N] [--penalties]
-                                      [--history]
+                                      [--history] [--beams K]
 """
 import argparse
 import json
@@ -96,14 +101,43 @@ def bench_sampler(B, cfg, top_k, top_p, reps, dev, procs=None, hist=None, contex
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
-def bench_decode(model, idx, a, lens=None, procs=None, hist=None):
-    ses = DecodeSession(model, idx, a.window + 1, 1.0, a.top_k or None, DeviceRNG(0, device=idx.device).state,
-                        eos=None if hist is None else hist.eos_token_id, top_p=a.top_p, prompt_lens=lens,
-                        processors=procs, history=hist)
+def bench_beam_step(B, K, cfg, reps, dev, context=512, all_equal=False):
+    """us per beam step (k_beam_rows, k_beam_merge and the tail), ``reps`` calls between one event pair; the table
+    copy is that of a row at position ``context`` and beyond.  ``all_equal``: every logit the same value, the
+    selection's worst case -- all ``K`` of a row's candidates are ties at the threshold, one pass over the row each"""
+    logits = (torch.randn(B * K, cfg.padded_vocab, device=dev) * 3).to(torch.bfloat16)
+    if all_equal:
+        logits.fill_(0.75)
+    bb = D.BeamBuffers(D.BeamConfig(K), torch.zeros(B, context, device=dev, dtype=torch.int64), None, 1,
+                       cfg.vocab_size, cfg.padded_vocab, dev, context + reps + 11)
+    bb.state.reset(pos=context, step=1)
+    for _ in range(10):
+        bb.sample(logits)
+    e0, e1 = events(1)[0]
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(reps):
+        bb.sample(logits)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps
+
+
+def bench_decode(model, idx, a, lens=None, procs=None, hist=None, beams=0):
+    if beams:
+        ses = DecodeSession(model, idx, a.window + 1, prompt_lens=lens, beam=D.BeamConfig(beams))
+    else:
+        ses = DecodeSession(model, idx, a.window + 1, 1.0, a.top_k or None, DeviceRNG(0, device=idx.device).state,
+                            eos=None if hist is None else hist.eos_token_id, top_p=a.top_p, prompt_lens=lens,
+                            processors=procs, history=hist)
     graph = ses.capture()
     start = (ses.state.buf.clone(), ses.next.clone(), None if ses.counts is None else ses.counts.buf.clone())
+    beam_start = ses.buffers.snapshot() if beams else None
 
     def rewind():
+        if beams:        # S, len and the state; the table keeps whatever rows of the group the last window left
+            ses.buffers.restore(beam_start)
+            return
         ses.state.buf.copy_(start[0])
         ses.next.copy_(start[1])
         if start[2] is not None:
@@ -163,6 +197,7 @@ def main():
     ap.add_argument("--sampler-reps", type=int, default=0, help="also time the sampler launch alone")
     ap.add_argument("--penalties", action="store_true", help="a second row per batch size with the logit processors on")
     ap.add_argument("--history", action="store_true", help="a further row with the history constraints on")
+    ap.add_argument("--beams", type=int, default=0, help="a further row with beam search: batch size / K prompts x K beams")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("gpt2_decode_bench: needs a GPU (no CPU fallback: a CPU time says nothing about the kernels)")
@@ -180,15 +215,25 @@ def main():
             mean_keys = sum(n + (a.window + 1) / 2.0 for n in (lens or [a.context] * B))
             kv_bytes = cfg.n_layer * 2 * cfg.n_head * mean_keys * 64 * 2
             pen = penalty_processors(cfg, dev) if a.penalties else None
-            rows = [(None, None)] + ([(pen, None)] if a.penalties else [])
-            rows += [(pen, history_constraints(cfg))] if a.history else []
-            for procs, hist in rows:
-                per_replay, per_window, eager = bench_decode(model, idx, a, lens, procs, hist)
+            rows = [(None, None, 0)] + ([(pen, None, 0)] if a.penalties else [])
+            rows += [(pen, history_constraints(cfg), 0)] if a.history else []
+            if a.beams:
+                if a.beams < 2 or B % a.beams:
+                    sys.exit(f"gpt2_decode_bench: --beams {a.beams} needs batch sizes that are multiples of it (got {B})")
+                rows.append((None, None, a.beams))
+            for procs, hist, beams in rows:
+                nb = B // beams if beams else B              # prompts of this row
+                per_replay, per_window, eager = bench_decode(model, idx[:nb], a, lens and lens[::beams or 1], procs,
+                                                             hist, beams)
                 if procs is None and hist is None and a.recompute_reps > 0:   # once per batch size, after the plain row
                     rec = bench_recompute(model, idx, a.recompute_reps)
                 extra = {"top_k": a.top_k, "top_p": a.top_p, "prompt_lens": lens, "penalties": procs is not None,
-                         "history": hist is not None}
-                if a.sampler_reps > 0:
+                         "history": hist is not None, "num_beams": beams or 1, "prompts": nb}
+                if a.sampler_reps > 0 and beams:
+                    extra["beam_step_us_per_launch"] = {
+                        "randn_x3": round(bench_beam_step(nb, beams, cfg, a.sampler_reps, dev, a.context), 2),
+                        "all_equal": round(bench_beam_step(nb, beams, cfg, a.sampler_reps, dev, a.context, True), 2)}
+                elif a.sampler_reps > 0:
                     k = a.top_k or None
                     args = (a.sampler_reps, dev, procs, hist, a.context)
                     extra["sampler_us_per_launch"] = {
