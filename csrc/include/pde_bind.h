@@ -58,5 +58,6 @@ constexpr auto F64 = at::kDouble;
 void register_transformer(pybind11::module& m);
 void register_resnet(pybind11::module& m);
 void register_decode(pybind11::module& m);
+void register_fp8(pybind11::module& m);
 
 }  // namespace pde

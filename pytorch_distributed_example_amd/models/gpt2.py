@@ -33,6 +33,7 @@ import torch
 import torch.nn as tnn
 
 from ..ops import decode as D
+from ..ops import fp8 as F8
 from ..ops import transformer as T
 from ..ops.rng import DeviceRNG
 
@@ -49,6 +50,7 @@ class GPTConfig:
     embd_pdrop: float = 0.0
     attn_pdrop: float = 0.0
     resid_pdrop: float = 0.0
+    fp8_forward: bool = False     # the four projections of every block run the FP8 (e4m3) forward GEMM (ops/fp8.py)
 
 
 class _LN(tnn.Module):
@@ -68,7 +70,9 @@ class _Linear(tnn.Module):
         self.weight = tnn.Parameter(torch.empty(fout, fin).normal_(0.0, std))
         self.bias = tnn.Parameter(torch.zeros(fout))
 
-    def forward(self, x):
+    def forward(self, x, fp8=False, wq=None):
+        if fp8:
+            return F8.linear_fp8(x, self.weight, self.bias, wq)
         return T.linear(x, self.weight, self.bias)
 
 
@@ -81,7 +85,11 @@ class _Attn(tnn.Module):
         self.c_attn = _Linear(C, 3 * C, 0.02)
         self.c_proj = _Linear(C, C, 0.02 / math.sqrt(2 * cfg.n_layer))
 
-    def forward(self, x, snap=None, site=0, doc_bounds=None):
+    def forward(self, x, snap=None, site=0, doc_bounds=None, fp8=None):
+        if fp8 is not None:             # FP8 forward projections: (c_attn's, c_proj's) quantised weights or Nones
+            p = 0.0 if snap is None else self.attn_pdrop
+            qkv = self.c_attn(x, True, fp8[0])
+            return self.c_proj(T.causal_attention(qkv, self.n_head, p, snap, site, doc_bounds=doc_bounds), True, fp8[1])
         if doc_bounds is not None:      # packed sequences (ops.doc_bounds), with or without dropout
             p = 0.0 if snap is None else self.attn_pdrop
             return self.c_proj(T.causal_attention(self.c_attn(x), self.n_head, p, snap, site, doc_bounds=doc_bounds))
@@ -97,7 +105,9 @@ class _MLP(tnn.Module):
         self.c_fc = _Linear(C, 4 * C, 0.02)
         self.c_proj = _Linear(4 * C, C, 0.02 / math.sqrt(2 * cfg.n_layer))
 
-    def forward(self, x):
+    def forward(self, x, fp8=None):
+        if fp8 is not None:
+            return F8.mlp_fp8(x, self.c_fc.weight, self.c_fc.bias, self.c_proj.weight, self.c_proj.bias, fp8[0], fp8[1])
         return T.mlp(x, self.c_fc.weight, self.c_fc.bias, self.c_proj.weight, self.c_proj.bias)
 
 
@@ -114,13 +124,18 @@ class Block(tnn.Module):
     def forward(self, x, delta=None):
         return sum(self.forward_deferred(x, delta))
 
-    def forward_deferred(self, x, delta=None, snap=None, doc_bounds=None):
+    def forward_deferred(self, x, delta=None, snap=None, doc_bounds=None, fp8=None):
         """(residual, mlp_out) with the block output = residual + mlp_out left unsummed, so the next
         LayerNorm adds it inside its kernel.  ``delta`` is the previous block's deferred mlp_out.
         (residual, LN(x)) come from one op: the residual-gradient add is fused into the LN backward.
         ``snap`` (an RNG snapshot of this forward) turns dropout on: the returned mlp_out is still
         undropped -- whoever adds it drops it under this layer's site ``3 + 3l``, as this block does
-        with the ``delta`` it is handed.  ``doc_bounds`` (``ops.doc_bounds``) masks attention per document."""
+        with the ``delta`` it is handed.  ``doc_bounds`` (``ops.doc_bounds``) masks attention per document.
+        ``fp8`` (``GPTConfig.fp8_forward``): the four projections run the FP8 forward; it holds their quantised
+        weights in the order c_attn, attention c_proj, c_fc, MLP c_proj, or ``None``s (each op then quantises
+        its own)."""
+        if fp8 is not None:
+            return self._forward_deferred_fp8(x, delta, snap, doc_bounds, fp8)
         if snap is not None:
             return self._forward_deferred_drop(x, delta, snap, doc_bounds)
         if delta is None:
@@ -130,6 +145,22 @@ class Block(tnn.Module):
         x, h = T.add_layer_norm_residual(x, self.attn(h, doc_bounds=doc_bounds), self.ln_2.weight, self.ln_2.bias,
                                          self.ln_2.eps)
         return x, self.mlp(h)
+
+    def _forward_deferred_fp8(self, x, delta, snap, doc_bounds, fp8):
+        l, p = self.layer_idx, self.resid_pdrop
+        ln1, ln2 = self.ln_1, self.ln_2
+        if delta is None:
+            x, h = T.layer_norm_residual(x, ln1.weight, ln1.bias, ln1.eps)
+        elif snap is None:
+            x, h = T.add_layer_norm_residual(x, delta, ln1.weight, ln1.bias, ln1.eps)
+        else:
+            x, h = T.add_dropout_layer_norm_residual(x, delta, ln1.weight, ln1.bias, ln1.eps, p, snap, 3 * l)
+        a = self.attn(h, snap, 1 + 3 * l, doc_bounds, fp8[:2])
+        if snap is None:
+            x, h = T.add_layer_norm_residual(x, a, ln2.weight, ln2.bias, ln2.eps)
+        else:
+            x, h = T.add_dropout_layer_norm_residual(x, a, ln2.weight, ln2.bias, ln2.eps, p, snap, 2 + 3 * l)
+        return x, self.mlp(h, fp8[2:])
 
     def forward_deferred_qkv(self, x, delta=None):
         """``forward_deferred`` without dropout that also returns this layer's c_attn output
@@ -191,6 +222,7 @@ class GPT(tnn.Module):
         self.transformer = _Transformer(cfg)
         self._rng = None          # DeviceRNG, created on first use (plain attribute: not a buffer)
         self._rng_init = (0, 0)
+        self._generating = False  # inside ``generate``: its CPU definition calls ``forward``, which then ignores fp8_forward
 
     @property
     def rng(self) -> DeviceRNG:
@@ -210,6 +242,17 @@ class GPT(tnn.Module):
         if self._rng is not None:
             self._rng.manual_seed(seed, stream)
         return self
+
+    def _fp8_weights(self):
+        """Per block, the quantised weights of its four projections (c_attn, attention c_proj, c_fc, MLP c_proj):
+        on the GPU all of them from one ``quantize_many`` call (two launches); on the CPU ``None``s, the ops
+        quantise their own."""
+        ws = [w for b in self.transformer.h
+              for w in (b.attn.c_attn.weight, b.attn.c_proj.weight, b.mlp.c_fc.weight, b.mlp.c_proj.weight)]
+        if not ws[0].is_cuda:
+            return [(None,) * 4] * len(self.transformer.h)
+        q = F8.quantize_many(ws)
+        return [tuple(q[i:i + 4]) for i in range(0, len(q), 4)]
 
     def dropout_active(self) -> bool:
         c = self.config
@@ -257,8 +300,12 @@ class GPT(tnn.Module):
         else:
             x = T.embedding(idx, t.wte.weight, t.wpe.weight, self.config.embd_pdrop, snap, 0)
         delta = None
-        for blk in t.h:
-            x, delta = blk.forward_deferred(x, delta, snap, bounds)
+        if self.config.fp8_forward and not self._generating:
+            for blk, wq in zip(t.h, self._fp8_weights()):
+                x, delta = blk.forward_deferred(x, delta, snap, bounds, wq)
+        else:
+            for blk in t.h:
+                x, delta = blk.forward_deferred(x, delta, snap, bounds)
         if delta is None:
             x = t.ln_f(x)
         elif snap is None:   # last block's residual add fused into ln_f (the summed stream itself is not needed)
@@ -385,6 +432,7 @@ class GPT(tnn.Module):
             generator.to(dev)
         was_training = self.training
         self.eval()
+        self._generating = True
         try:
             with torch.no_grad():
                 args = (idx.to(dev).long(), max_new_tokens, config, generator, prompt_lens, int(pad_token_id),
@@ -393,6 +441,7 @@ class GPT(tnn.Module):
                     return self._generate_gpu(*args, use_graph, _after_prefill)
                 return self._generate_cpu(*args)
         finally:
+            self._generating = False
             self.train(was_training)
 
     def _generate_beam(self, idx, n_new, beam, lens, pad, return_logits, return_beams, use_graph, _after_prefill,
@@ -402,6 +451,7 @@ class GPT(tnn.Module):
         ``beam_step_reference``) -- and the rows' final ``S``, ``len`` and ``finished``."""
         was_training = self.training
         self.eval()
+        self._generating = True
         try:
             with torch.no_grad():
                 if idx.is_cuda:
@@ -410,6 +460,7 @@ class GPT(tnn.Module):
                 else:
                     out, scores, logits, tr = self._generate_beam_cpu(idx, n_new, beam, lens, pad, return_logits)
         finally:
+            self._generating = False
             self.train(was_training)
         if trace is not None:
             trace.update(tr)
