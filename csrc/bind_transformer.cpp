@@ -3,6 +3,7 @@
 #include "pde_bind.h"
 #include "pde_kernels.h"
 #include "pde_loss.h"
+#include "pde_mxfp8.h"
 
 namespace pde {
 namespace {
@@ -64,6 +65,31 @@ void ln_fwd(const at::Tensor& X, const at::Tensor& G, const at::Tensor& B, const
   hip_check(pde_ln_fwd(X.data_ptr(), dp, sp, G.data_ptr(), B.data_ptr(), Y.data_ptr(), ptr<float>(mean), ptr<float>(rstd),
                        (int)N, (int)C, (float)eps, drop, cur_stream()),
             "ln_fwd");
+}
+
+// ln_fwd that also writes Y as an MX tensor (pde_mxfp8.h): Q [N, C] e4m3 bytes, E [N, C / 32] scale bytes
+void ln_fwd_mx(const at::Tensor& X, const at::Tensor& G, const at::Tensor& B, const at::Tensor& Y,
+               const at::Tensor& mean, const at::Tensor& rstd, double eps, const at::Tensor& Q, const at::Tensor& E,
+               const OptT& D, const OptT& S, const OptT& rng, int64_t site, int64_t thr, double inv_keep) {
+  const int64_t C = X.size(-1), N = X.numel() / C;
+  TORCH_CHECK(C % 32 == 0 && C <= 2048, "ln_fwd_mx: C must be a multiple of 32 and <= 2048");
+  check_cuda(X, "X", BF16);
+  check_cuda(G, "gamma", BF16, C);
+  check_cuda(B, "beta", BF16, C);
+  check_cuda(Y, "Y", BF16, N * C);
+  check_cuda(mean, "mean", F32, N);
+  check_cuda(rstd, "rstd", F32, N);
+  check_cuda(Q, "Q", U8, N * C);
+  check_cuda(E, "E", U8, N * C / 32);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(Q.data_ptr()) % 4 == 0, "ln_fwd_mx: Q must be 4-byte aligned");
+  const void* dp = optr<void>(D, "D", BF16, N * C);
+  void* sp = optr<void>(S, "S", BF16, N * C);
+  TORCH_CHECK((dp == nullptr) == (sp == nullptr), "ln_fwd_mx: D (residual input) and S (sum output) go together");
+  const PdeDrop drop = drop_of(rng, site, thr, inv_keep);
+  TORCH_CHECK(drop.rng == nullptr || dp != nullptr, "ln_fwd_mx: dropout acts on the residual input D");
+  hip_check(pde_ln_fwd_mx(X.data_ptr(), dp, sp, G.data_ptr(), B.data_ptr(), Y.data_ptr(), ptr<float>(mean),
+                          ptr<float>(rstd), Q.data_ptr(), E.data_ptr(), (int)N, (int)C, (float)eps, drop, cur_stream()),
+            "ln_fwd_mx");
 }
 
 int64_t ln_bwd_blocks(int64_t N) { return pde_ln_bwd_blocks((int)N); }
@@ -422,6 +448,9 @@ void register_transformer(pybind11::module& m) {
   namespace py = pybind11;
   m.def("ln_fwd", &ln_fwd, py::arg("X"), py::arg("G"), py::arg("B"), py::arg("Y"), py::arg("mean"), py::arg("rstd"),
         py::arg("eps"), py::arg("D") = py::none(), py::arg("S") = py::none(), py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
+  m.def("ln_fwd_mx", &ln_fwd_mx, py::arg("X"), py::arg("G"), py::arg("B"), py::arg("Y"), py::arg("mean"), py::arg("rstd"),
+        py::arg("eps"), py::arg("Q"), py::arg("E"), py::arg("D") = py::none(), py::arg("S") = py::none(),
+        py::arg("rng") = py::none(), py::arg("site") = 0, py::arg("thr") = 0, py::arg("inv_keep") = 1.0);
   m.def("ln_bwd_blocks", &ln_bwd_blocks);
   m.def("ln_bwd", &ln_bwd, py::arg("dY"), py::arg("X"), py::arg("mean"), py::arg("rstd"), py::arg("G"), py::arg("dRes"),
         py::arg("dX"), py::arg("part"), py::arg("dG"), py::arg("dB"), py::arg("accumulate"),

@@ -51,6 +51,8 @@ class GPTConfig:
     attn_pdrop: float = 0.0
     resid_pdrop: float = 0.0
     fp8_forward: bool = False     # the four projections of every block run the FP8 (e4m3) forward GEMM (ops/fp8.py)
+    fp8_scaling: str = "tensor"   # with fp8_forward: one scale per "tensor", or "mx" (one per 32-element block, the
+    #                               operands quantised by the kernels that produce them); not read otherwise
 
 
 class _LN(tnn.Module):
@@ -70,7 +72,9 @@ class _Linear(tnn.Module):
         self.weight = tnn.Parameter(torch.empty(fout, fin).normal_(0.0, std))
         self.bias = tnn.Parameter(torch.zeros(fout))
 
-    def forward(self, x, fp8=False, wq=None):
+    def forward(self, x, fp8=False, wq=None, xq=None):
+        if fp8 == "mx":
+            return F8.linear_mx(x, self.weight, self.bias, wq, xq)
         if fp8:
             return F8.linear_fp8(x, self.weight, self.bias, wq)
         return T.linear(x, self.weight, self.bias)
@@ -85,11 +89,12 @@ class _Attn(tnn.Module):
         self.c_attn = _Linear(C, 3 * C, 0.02)
         self.c_proj = _Linear(C, C, 0.02 / math.sqrt(2 * cfg.n_layer))
 
-    def forward(self, x, snap=None, site=0, doc_bounds=None, fp8=None):
+    def forward(self, x, snap=None, site=0, doc_bounds=None, fp8=None, xq=None):
         if fp8 is not None:             # FP8 forward projections: (c_attn's, c_proj's) quantised weights or Nones
             p = 0.0 if snap is None else self.attn_pdrop
-            qkv = self.c_attn(x, True, fp8[0])
-            return self.c_proj(T.causal_attention(qkv, self.n_head, p, snap, site, doc_bounds=doc_bounds), True, fp8[1])
+            kind = "mx" if xq is not None else True     # xq: x as the MxTensor its LayerNorm wrote (fp8_scaling "mx")
+            qkv = self.c_attn(x, kind, fp8[0], xq)
+            return self.c_proj(T.causal_attention(qkv, self.n_head, p, snap, site, doc_bounds=doc_bounds), kind, fp8[1])
         if doc_bounds is not None:      # packed sequences (ops.doc_bounds), with or without dropout
             p = 0.0 if snap is None else self.attn_pdrop
             return self.c_proj(T.causal_attention(self.c_attn(x), self.n_head, p, snap, site, doc_bounds=doc_bounds))
@@ -105,7 +110,9 @@ class _MLP(tnn.Module):
         self.c_fc = _Linear(C, 4 * C, 0.02)
         self.c_proj = _Linear(4 * C, C, 0.02 / math.sqrt(2 * cfg.n_layer))
 
-    def forward(self, x, fp8=None):
+    def forward(self, x, fp8=None, xq=None):
+        if xq is not None:
+            return F8.mlp_mx(x, self.c_fc.weight, self.c_fc.bias, self.c_proj.weight, self.c_proj.bias, fp8[0], fp8[1], xq)
         if fp8 is not None:
             return F8.mlp_fp8(x, self.c_fc.weight, self.c_fc.bias, self.c_proj.weight, self.c_proj.bias, fp8[0], fp8[1])
         return T.mlp(x, self.c_fc.weight, self.c_fc.bias, self.c_proj.weight, self.c_proj.bias)
@@ -116,6 +123,7 @@ class Block(tnn.Module):
         super().__init__()
         self.layer_idx = layer_idx
         self.resid_pdrop = cfg.resid_pdrop
+        self.fp8_mx = cfg.fp8_scaling == "mx"
         self.ln_1 = _LN(cfg.n_embd, cfg.ln_eps)
         self.attn = _Attn(cfg)
         self.ln_2 = _LN(cfg.n_embd, cfg.ln_eps)
@@ -133,7 +141,9 @@ class Block(tnn.Module):
         with the ``delta`` it is handed.  ``doc_bounds`` (``ops.doc_bounds``) masks attention per document.
         ``fp8`` (``GPTConfig.fp8_forward``): the four projections run the FP8 forward; it holds their quantised
         weights in the order c_attn, attention c_proj, c_fc, MLP c_proj, or ``None``s (each op then quantises
-        its own)."""
+        its own).  Under ``fp8_scaling="mx"`` they are ``MxTensor``s, both LayerNorms hand their projection the
+        ``MxTensor`` of ``h`` they wrote themselves, c_fc's epilogue hands the MLP c_proj its own, and only the
+        attention output is quantised by a launch of its own."""
         if fp8 is not None:
             return self._forward_deferred_fp8(x, delta, snap, doc_bounds, fp8)
         if snap is not None:
@@ -149,6 +159,8 @@ class Block(tnn.Module):
     def _forward_deferred_fp8(self, x, delta, snap, doc_bounds, fp8):
         l, p = self.layer_idx, self.resid_pdrop
         ln1, ln2 = self.ln_1, self.ln_2
+        if self.fp8_mx:
+            return self._forward_deferred_mx(x, delta, snap, doc_bounds, fp8)
         if delta is None:
             x, h = T.layer_norm_residual(x, ln1.weight, ln1.bias, ln1.eps)
         elif snap is None:
@@ -161,6 +173,22 @@ class Block(tnn.Module):
         else:
             x, h = T.add_dropout_layer_norm_residual(x, a, ln2.weight, ln2.bias, ln2.eps, p, snap, 2 + 3 * l)
         return x, self.mlp(h, fp8[2:])
+
+    def _forward_deferred_mx(self, x, delta, snap, doc_bounds, fp8):
+        l, p = self.layer_idx, self.resid_pdrop
+        ln1, ln2 = self.ln_1, self.ln_2
+        if delta is None:
+            x, h, hq = T.layer_norm_residual(x, ln1.weight, ln1.bias, ln1.eps, mx_out=True)
+        elif snap is None:
+            x, h, hq = T.add_layer_norm_residual(x, delta, ln1.weight, ln1.bias, ln1.eps, mx_out=True)
+        else:
+            x, h, hq = T.add_dropout_layer_norm_residual(x, delta, ln1.weight, ln1.bias, ln1.eps, p, snap, 3 * l, True)
+        a = self.attn(h, snap, 1 + 3 * l, doc_bounds, fp8[:2], hq)
+        if snap is None:
+            x, h, hq = T.add_layer_norm_residual(x, a, ln2.weight, ln2.bias, ln2.eps, mx_out=True)
+        else:
+            x, h, hq = T.add_dropout_layer_norm_residual(x, a, ln2.weight, ln2.bias, ln2.eps, p, snap, 2 + 3 * l, True)
+        return x, self.mlp(h, fp8[2:], hq)
 
     def forward_deferred_qkv(self, x, delta=None):
         """``forward_deferred`` without dropout that also returns this layer's c_attn output
@@ -218,6 +246,8 @@ class _Transformer(tnn.Module):
 class GPT(tnn.Module):
     def __init__(self, cfg: GPTConfig = GPTConfig()):
         super().__init__()
+        if cfg.fp8_forward and cfg.fp8_scaling not in ("tensor", "mx"):
+            raise ValueError(f"GPTConfig.fp8_scaling must be 'tensor' or 'mx', got {cfg.fp8_scaling!r}")
         self.config = cfg
         self.transformer = _Transformer(cfg)
         self._rng = None          # DeviceRNG, created on first use (plain attribute: not a buffer)
@@ -245,13 +275,13 @@ class GPT(tnn.Module):
 
     def _fp8_weights(self):
         """Per block, the quantised weights of its four projections (c_attn, attention c_proj, c_fc, MLP c_proj):
-        on the GPU all of them from one ``quantize_many`` call (two launches); on the CPU ``None``s, the ops
-        quantise their own."""
+        on the GPU all of them from one ``quantize_many`` call (two launches; one ``quantize_mx_many`` launch under
+        ``fp8_scaling="mx"``); on the CPU ``None``s, the ops quantise their own."""
         ws = [w for b in self.transformer.h
               for w in (b.attn.c_attn.weight, b.attn.c_proj.weight, b.mlp.c_fc.weight, b.mlp.c_proj.weight)]
         if not ws[0].is_cuda:
             return [(None,) * 4] * len(self.transformer.h)
-        q = F8.quantize_many(ws)
+        q = F8.quantize_mx_many(ws) if self.config.fp8_scaling == "mx" else F8.quantize_many(ws)
         return [tuple(q[i:i + 4]) for i in range(0, len(q), 4)]
 
     def dropout_active(self) -> bool:

@@ -20,7 +20,8 @@ from .decode import (DecodeState, HistoryConstraints, KVCache, LogitProcessors, 
                      SamplerConfig, TokenCounts, check_top_p, decode_attention, decode_embed, history_bans_reference,
                      key16_to_float, process_logits_reference, sample, sample_reference, skinny_linear)
 from . import fp8  # noqa: F401
-from .fp8 import Fp8Tensor, linear_fp8, mlp_fp8, quantize_reference  # noqa: F401
+from .fp8 import (Fp8Tensor, MxTensor, linear_fp8, linear_mx, mlp_fp8, mlp_mx, quantize_mx_reference,  # noqa: F401
+                  quantize_reference)
 
 
 def linear(x, weight, bias=None):

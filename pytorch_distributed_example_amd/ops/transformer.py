@@ -64,7 +64,11 @@ class LayerNormFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
-def layer_norm(x, weight, bias, eps: float = 1e-5):
+def layer_norm(x, weight, bias, eps: float = 1e-5, mx_out: bool = False):
+    """``mx_out=True`` (here and in the three ops below): the last output is joined by its ``ops.fp8.MxTensor``, written
+    by the same kernel, bit for bit ``ops.fp8.quantize_mx`` of it and not differentiable; needs ``C % 32 == 0``."""
+    if mx_out:
+        return _with_mx(LayerNormMxFn, x, (weight, bias, eps), lambda: (layer_norm(x, weight, bias, eps),))
     if _gpu(x):
         return LayerNormFn.apply(x, weight, bias, eps)
     return F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
@@ -106,8 +110,10 @@ class LayerNormResFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
-def layer_norm_residual(x, weight, bias, eps: float = 1e-5):
+def layer_norm_residual(x, weight, bias, eps: float = 1e-5, mx_out: bool = False):
     """Returns ``(x, layer_norm(x))``; use the first output as the residual stream."""
+    if mx_out:
+        return _with_mx(LayerNormResMxFn, x, (weight, bias, eps), lambda: layer_norm_residual(x, weight, bias, eps))
     if _gpu(x):
         return LayerNormResFn.apply(x, weight, bias, eps)
     return x, F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
@@ -138,9 +144,12 @@ class AddLayerNormResFn(torch.autograd.Function):
         return dx, dx, dw, db, None
 
 
-def add_layer_norm_residual(x, d, weight, bias, eps: float = 1e-5):
+def add_layer_norm_residual(x, d, weight, bias, eps: float = 1e-5, mx_out: bool = False):
     """Returns ``(x + d, layer_norm(x + d))`` (the residual stream and the normalised input of the
     next sub-block); on GPU the add is fused into the LayerNorm kernel."""
+    if mx_out and not (_gpu(x) and (x.shape != d.shape or x.dtype != d.dtype)):
+        return _with_mx(AddLayerNormResMxFn, x, (d, weight, bias, eps),
+                        lambda: add_layer_norm_residual(x, d, weight, bias, eps))
     if _gpu(x):
         # no silent ATen fallback on the GPU (verdict r3 weak 6)
         if x.shape != d.shape or x.dtype != d.dtype:
@@ -207,13 +216,16 @@ class AddDropLayerNormResFn(torch.autograd.Function):
 
 
 def add_dropout_layer_norm_residual(x, d, weight, bias, eps: float = 1e-5, p: float = 0.0, rng_snapshot=None,
-                                    site: int = 0):
+                                    site: int = 0, mx_out: bool = False):
     """Returns ``(s, layer_norm(s))`` with ``s = x + dropout(d, p)`` (residual dropout): the mask of
     ``(rng_snapshot, site)`` and the ``1 / keep`` scale run inside the fused add + LayerNorm kernel,
     forward and backward.  ``p == 0`` is ``add_layer_norm_residual``."""
     if p == 0.0:
-        return add_layer_norm_residual(x, d, weight, bias, eps)
+        return add_layer_norm_residual(x, d, weight, bias, eps, mx_out)
     thr, ik = _drop_args(p, rng_snapshot, "elementwise")
+    if mx_out and not (_gpu(x) and (x.shape != d.shape or x.dtype != d.dtype)):
+        return _with_mx(AddDropLayerNormResMxFn, x, (d, weight, bias, eps, rng_snapshot, int(site), thr, ik),
+                        lambda: add_dropout_layer_norm_residual(x, d, weight, bias, eps, p, rng_snapshot, site))
     if _gpu(x):
         if x.shape != d.shape or x.dtype != d.dtype:
             raise NotImplementedError(f"add_dropout_layer_norm_residual on GPU needs x and d of one shape and dtype "
@@ -221,6 +233,95 @@ def add_dropout_layer_norm_residual(x, d, weight, bias, eps: float = 1e-5, p: fl
         return AddDropLayerNormResFn.apply(x, d, weight, bias, eps, rng_snapshot, int(site), thr, ik)
     s = x + _cpu_drop(d, p, rng_snapshot, site)
     return s, F.layer_norm(s, (s.shape[-1],), weight, bias, eps)
+
+
+# --------------------------------------------------------------------------------------- LayerNorm, MX output
+def _ln_fwd_mx(xc, w, b, eps, *rest):
+    """``ln_fwd_mx`` (csrc/kernels/gemm_mxfp8.hip): ``ln_fwd`` that also writes ``y`` as an ``ops.fp8.MxTensor``."""
+    C = xc.shape[-1]
+    N = xc.numel() // C
+    y = torch.empty_like(xc)
+    mean = torch.empty(N, device=xc.device, dtype=torch.float32)
+    rstd = torch.empty(N, device=xc.device, dtype=torch.float32)
+    qd = torch.empty(xc.shape, device=xc.device, dtype=torch.uint8)
+    qs = torch.empty(*xc.shape[:-1], C // 32, device=xc.device, dtype=torch.uint8)
+    kernels().ln_fwd_mx(xc, w, b, y, mean, rstd, eps, qd, qs, *rest)
+    return y, mean, rstd, qd.view(torch.float8_e4m3fn), qs
+
+
+def _with_mx(fn, x, args, plain):
+    """The outputs of ``fn`` (GPU) or of ``plain()`` (CPU) with the last two / a reference quantisation as an
+    ``MxTensor``."""
+    from .fp8 import MxTensor, quantize_mx_reference
+    if x.shape[-1] % 32:
+        raise ValueError(f"layer norm with mx_out needs C % 32 == 0 (got C = {x.shape[-1]})")
+    if _gpu(x):
+        out = fn.apply(x, *args)
+        return out[:-2] + (MxTensor(*out[-2:]),)
+    out = plain()
+    return out + (quantize_mx_reference(out[-1]),)
+
+
+class LayerNormMxFn(LayerNormFn):
+    @staticmethod
+    def forward(ctx, x, w, b, eps):
+        xc = _c(x)
+        y, mean, rstd, qd, qs = _ln_fwd_mx(xc, w, b, eps)
+        ctx.save_for_backward(xc, w, mean, rstd)
+        ctx.mark_non_differentiable(qd, qs)
+        return y, qd, qs
+
+    @staticmethod
+    def backward(ctx, dy, _qd, _qs):
+        return LayerNormFn.backward(ctx, dy)
+
+
+class LayerNormResMxFn(LayerNormResFn):
+    @staticmethod
+    def forward(ctx, x, w, b, eps):
+        xc = _c(x)
+        y, mean, rstd, qd, qs = _ln_fwd_mx(xc, w, b, eps)
+        ctx.save_for_backward(xc, w, b, mean, rstd)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(qd, qs)
+        return xc.view_as(xc), y, qd, qs
+
+    @staticmethod
+    def backward(ctx, dres, dy, _qd, _qs):
+        return LayerNormResFn.backward(ctx, dres, dy)
+
+
+class AddLayerNormResMxFn(AddLayerNormResFn):
+    @staticmethod
+    def forward(ctx, x, d, w, b, eps):
+        xc, dc = _c(x), _c(d)
+        s = torch.empty_like(xc)
+        y, mean, rstd, qd, qs = _ln_fwd_mx(xc, w, b, eps, dc, s)
+        ctx.save_for_backward(s, w, b, mean, rstd)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(qd, qs)
+        return s, y, qd, qs
+
+    @staticmethod
+    def backward(ctx, dres, dy, _qd, _qs):
+        return AddLayerNormResFn.backward(ctx, dres, dy)
+
+
+class AddDropLayerNormResMxFn(AddDropLayerNormResFn):
+    @staticmethod
+    def forward(ctx, x, d, w, b, eps, snap, site, thr, ik):
+        xc, dc = _c(x), _c(d)
+        s = torch.empty_like(xc)
+        y, mean, rstd, qd, qs = _ln_fwd_mx(xc, w, b, eps, dc, s, snap, site, thr, ik)
+        ctx.save_for_backward(s, w, b, mean, rstd, snap)
+        ctx.drop = (site, thr, ik)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(qd, qs)
+        return s, y, qd, qs
+
+    @staticmethod
+    def backward(ctx, dres, dy, _qd, _qs):
+        return AddDropLayerNormResFn.backward(ctx, dres, dy)
 
 
 # --------------------------------------------------------------------------------------- GELU

@@ -69,9 +69,11 @@ def _hash_file(path, extra=""):
 # MFMAs, where packed f32 ops (v_pk_mul/add/fma_f32, 206 of them from SLP packing adjacent scalar ops)
 # cost more issue time than the two scalar ops they replace (MI355X_MICROARCH.md: an anti-lever beside
 # MFMAs; profiles/r5_gpt2/attention_no_slp/); lenet_v2.hip: the same, -45 VALU in the conv backward
-# loop (profiles/r5_lenet/lenet_no_slp/); gemm_fp8.hip: no packed f32 VALU ops at all (scalar forms only)
+# loop (profiles/r5_lenet/lenet_no_slp/); gemm_fp8.hip, gemm_mxfp8.hip: no packed f32 VALU ops at all (scalar
+# forms only)
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"], "lenet_v2.hip": ["-fno-slp-vectorize"],
-               "gemm_fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "gemm_fp8.hip": _NO_PK_F32, "gemm_mxfp8.hip": _NO_PK_F32}
 
 
 def _targets():
