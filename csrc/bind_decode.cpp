@@ -383,6 +383,89 @@ void cache_fill_beam(const at::Tensor& qkv, const at::Tensor& cache, int64_t T0,
             "cache_fill");
 }
 
+// ------------------------------------------------------------------------------------------ speculative decoding
+// qkv: [R = B * q, 3 * H * 64]; cache: one layer [2, B, H, Tmax, 64]; part: R * H * chunks * 66 floats; out: [R, H * 64]
+void decode_attention_spec(const at::Tensor& qkv, const at::Tensor& cache, const at::Tensor& state,
+                           const at::Tensor& part, const at::Tensor& out, int64_t H, double scale, int64_t q) {
+  TORCH_CHECK(qkv.dim() == 2 && H >= 1 && qkv.size(1) == 3 * H * 64, "decode_attention: qkv must be [R, 3 * H * 64]");
+  const int64_t R = qkv.size(0);
+  TORCH_CHECK(q >= 1 && R >= 1 && R <= PDE_DS_MAX_ROWS && R % q == 0, "decode_attention: R = B * q <= ",
+              PDE_DS_MAX_ROWS, " rows, got R ", R, ", q ", q);
+  check_cuda(qkv, "qkv", BF16);
+  check_al16(qkv, "qkv");
+  check_cache(cache, R / q, H);
+  const int64_t Tmax = cache.size(3), nch = (Tmax + pde_decode_attn_chunk() - 1) / pde_decode_attn_chunk();
+  check_state(state);
+  check_cuda(part, "part", F32, R * H * nch * 66);
+  check_cuda(out, "out", BF16, R * H * 64);
+  PdeSpecRows s{};
+  s.q = (int)q;
+  hip_check(pde_decode_attention_spec(qkv.data_ptr(), cache.data_ptr(), ptr<int>(state), ptr<float>(part),
+                                      out.data_ptr(), (int)R, (int)H, (int)Tmax, (float)scale, s, cur_stream()),
+            "decode_attention");
+}
+
+// One verify launch (PdeSpec in pde_decode.h).  logits: bf16 [B * q_in, Vp] with q_in = 1 (after the prefill) or K + 1;
+// next: int64 [B * (K + 1)]; out: int64 [B, width]; len / n / steps / accepted: int32 [B]; arg: int32 [B * (K + 1)];
+// done: int32 [1]; logits_out: bf16 [B, max_new, V] or None.
+void spec_step(const at::Tensor& logits, int64_t V, int64_t K, const at::Tensor& state, const at::Tensor& next,
+               const at::Tensor& out, const OptT& logits_out, const at::Tensor& len, const at::Tensor& n,
+               const at::Tensor& steps, const at::Tensor& accepted, const at::Tensor& arg, const at::Tensor& done,
+               int64_t max_new, int64_t n_pos, int64_t ngram, int64_t eos) {
+  check_cuda(logits, "logits", BF16);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) % 8 == 0, "spec_step: logits must be [rows, Vp] with Vp % 8 == 0");
+  check_cuda(len, "len", I32);
+  const int64_t B = len.numel(), Vp = logits.size(1), R = B * (K + 1);
+  TORCH_CHECK(K >= 1 && B >= 1 && R <= PDE_DS_MAX_ROWS, "spec_step: B * (K + 1) <= ", PDE_DS_MAX_ROWS, " rows, got B ", B,
+              ", K ", K);
+  TORCH_CHECK(logits.size(0) == B || logits.size(0) == R, "spec_step: logits hold B or B * (K + 1) rows, got ",
+              logits.size(0));
+  TORCH_CHECK(V >= 1 && V <= Vp && eos >= -1 && eos < V, "spec_step: 1 <= V <= Vp and eos in [-1, V)");
+  TORCH_CHECK(ngram >= 1 && ngram <= PDE_HIST_MAX_NGRAM, "spec_step: draft_ngram in 1 .. ", PDE_HIST_MAX_NGRAM, ", got ",
+              ngram);
+  TORCH_CHECK(max_new >= 1 && n_pos >= 1, "spec_step: max_new >= 1 and n_pos >= 1");
+  check_al16(logits, "logits");
+  check_state(state);
+  check_cuda(next, "next", I64, R);
+  check_cuda(out, "out", I64);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == B, "spec_step: out must be [B, width]");
+  check_cuda(n, "n", I32, B);
+  check_cuda(steps, "steps", I32, B);
+  check_cuda(accepted, "accepted", I32, B);
+  check_cuda(arg, "arg", I32, R);
+  check_cuda(done, "done", I32, 1);
+  PdeSpec a{};
+  a.logits = logits.data_ptr();
+  a.state = ptr<int>(state);
+  a.next = ptr<int64_t>(next);
+  a.out = ptr<int64_t>(out);
+  a.logits_out = nullptr;
+  if (given(logits_out)) {
+    check_cuda(*logits_out, "logits_out", BF16, B * max_new * V);
+    TORCH_CHECK(logits_out->dim() == 3 && logits_out->size(0) == B && logits_out->size(1) == max_new &&
+                    logits_out->size(2) == V,
+                "spec_step: logits_out must be [B, max_new, V]");
+    a.logits_out = logits_out->data_ptr();
+  }
+  a.len = ptr<int>(len);
+  a.n = ptr<int>(n);
+  a.steps = ptr<int>(steps);
+  a.accepted = ptr<int>(accepted);
+  a.arg = ptr<int>(arg);
+  a.done = ptr<int>(done);
+  a.B = (int)B;
+  a.K = (int)K;
+  a.q_in = (int)(logits.size(0) / B);
+  a.V = (int)V;
+  a.Vp = (int)Vp;
+  a.out_stride = (int)out.size(1);
+  a.max_new = (int)max_new;
+  a.n_pos = (int)n_pos;
+  a.ngram = (int)ngram;
+  a.eos = (int)eos;
+  hip_check(pde_spec_step(a, cur_stream()), "spec_step");
+}
+
 }  // namespace
 
 void register_decode(pybind11::module& m) {
@@ -409,6 +492,10 @@ void register_decode(pybind11::module& m) {
         py::arg("logits_out"), py::arg("eos"));
   m.def("beam_finalize", &beam_finalize);
   m.def("cache_fill_beam", &cache_fill_beam);
+  m.def("decode_attention_spec", &decode_attention_spec);
+  m.def("spec_step", &spec_step, py::arg("logits"), py::arg("V"), py::arg("K"), py::arg("state"), py::arg("next"),
+        py::arg("out"), py::arg("logits_out"), py::arg("len"), py::arg("n"), py::arg("steps"), py::arg("accepted"),
+        py::arg("arg"), py::arg("done"), py::arg("max_new"), py::arg("n_pos"), py::arg("ngram"), py::arg("eos"));
   m.attr("DECODE_STATE_WORDS") = PDE_DS_WORDS;
 }
 

@@ -186,6 +186,54 @@ hipError_t pde_beam_finalize(PdeBeamFinal a, hipStream_t st);
 hipError_t pde_cache_fill_beam(const void* qkv, void* cache, int B, int K, int H, int Tpad, int T0, int Tmax,
                                hipStream_t st);
 
+// ------------------------------------------------------------------------------------------ speculative decoding
+// Greedy generation with K = num_draft_tokens guessed continuations per prompt (definition: ops/decode.py).  Prompt b
+// owns the q = K + 1 physical rows r = b * q + i of the R = B * q <= PDE_DS_MAX_ROWS rows of a decode step: row 0
+// carries the last committed token, row i >= 1 draft d_i at the position i further on.  The KV cache has B rows, one
+// per prompt; the rows of a group read the group's committed prefix from it and each other's new keys from the
+// c_attn output of the same launch.
+//
+//   state      word 4 (PDE_DS_POS) stays 0 and is never advanced; the offset words 24..39 hold the rows' absolute
+//              positions, rewritten per group by every verify launch (so they are positive here), and the existing
+//              kernels keep reading p_r = state[PDE_DS_POS] + state[PDE_DS_OFF + r].  Words 8 + b, b < B, are the
+//              groups' finished flags (eos emitted or max_new tokens generated); word 5 is not used.
+//   idle rows  a row that can no longer contribute -- every row of a finished group, and draft row i of a live one
+//              when i exceeds the remaining budget - 1 or its position would reach n_pos -- is parked on row 0's
+//              position and token.  It then computes what row 0 computes and appends the same bytes to the same
+//              cache slot, and the acceptance never looks at it.
+typedef struct PdeSpecRows {
+  int q;                  // rows per group
+} PdeSpecRows;
+// pde_decode_attention for R = B * q rows over a cache of B rows [2][B][H][Tmax][64].  With P_b the position of row
+// b * q, row r = b * q + i at p_r reads key j < P_b from cache row b, key P_b <= j < p_r from the c_attn row of
+// sibling b * q + (j - P_b) (never from a row >= r), key p_r from its own c_attn row, and appends its K and V to
+// cache row b at p_r.  part: R * H * ceil(Tmax / chunk) * 66 floats; out: [R, H * 64]
+hipError_t pde_decode_attention_spec(const void* qkv, void* cache, const int* state, float* part, void* out, int R,
+                                     int H, int Tmax, float scale, PdeSpecRows s, hipStream_t st);
+
+// One verify launch: a block per logits row finds g_r (lowest index of the maximum over the first V columns), a block
+// per group applies the acceptance rule, emits, and drafts the next step's rows by prompt lookup over out[b, 0 : L],
+// and a one-thread tail sets `done`.  q_in = 1 is the launch after the prefill: one logits row per prompt, one token
+// emitted, `steps` not counted.  A finished group changes nothing, so a launch after `done` is a no-op.
+typedef struct PdeSpec {
+  const void* logits;     // [B * q_in, Vp] bf16
+  int* state;             // PDE_DS_WORDS
+  int64_t* next;          // [B * (K + 1)]: in, the rows' tokens (drafts in rows i >= 1); out, those of the next step
+  int64_t* out;           // [B, out_stride], the prompts in place; tokens go to out[b, len_b + n_b ..]
+  void* logits_out;       // [B, max_new, V] bf16 or null: slot n_b + i receives the logits g_i was taken from
+  const int* len;         // [B] prompt lengths
+  int* n;                 // [B] tokens generated so far
+  int* steps;             // [B] model steps the group took part in
+  int* accepted;          // [B] drafts whose token was emitted
+  int* arg;               // [B * (K + 1)] workspace: g_r
+  int* done;              // one word: every group is finished
+  int B, K, q_in, V, Vp, out_stride, max_new;
+  int n_pos;              // positions the model has (wpe rows)
+  int ngram;              // longest suffix the lookup tries, 1 .. PDE_HIST_MAX_NGRAM
+  int eos;                // -1: none
+} PdeSpec;
+hipError_t pde_spec_step(PdeSpec a, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,23 @@
-// The decode attention of the GPT-2 decode step: device code shared by two translation units.
+// The decode attention of the GPT-2 decode step: device code shared by three translation units.
 // decode.hip instantiates the plain kernel (k_dec_attn<>), decode_beam.hip the one that reads the keys through a
-// beam search's ancestor table (k_dec_attn<PdeBeamTable>).  As with the sampler (decode_sample.h) the extra
-// arguments travel in a by-value struct that only the second instantiation takes, and the two are compiled apart,
-// so the plain kernel keeps its argument layout and its instruction stream.  Include inside the unit's anonymous
+// beam search's ancestor table (k_dec_attn<PdeBeamTable>), decode_spec.hip the one whose rows share a cache row per
+// group and read each other's new keys (k_dec_attn<PdeSpecRows>).  As with the sampler (decode_sample.h) the extra
+// arguments travel in a by-value struct that only that instantiation takes, and they are compiled apart, so the
+// plain kernel keeps its argument layout and its instruction stream.  Include inside the unit's anonymous
 // namespace, after pde_hip.h, pde_bf16.h and pde_decode.h.
 #pragma once
 
 constexpr int DC_CH = 128;      // keys per block
 constexpr int DC_PART = 66;     // floats per partial: max, sum, 64 outputs
 
+// which instantiation this is: the one extra argument's type, if any
+template <typename T, typename... Ts>
+constexpr bool dec_attn_is = false;
+template <typename T>
+constexpr bool dec_attn_is<T, T> = true;
+
+// rows per group (PdeSpecRows in pde_decode.h)
+__device__ __forceinline__ int spec_rows(const PdeSpecRows& s) { return s.q; }
 // the table half that the step at hand reads, row b (PdeBeamTable in pde_decode.h)
 __device__ __forceinline__ const unsigned char* beam_anc(const int* state, int b, const PdeBeamTable& t) {
   return t.anc + ((size_t)(state[PDE_DS_STEP] & 1) * PDE_DS_MAX_ROWS + b) * t.stride;
@@ -23,11 +32,15 @@ __device__ __forceinline__ const unsigned char* beam_anc(const int* state, int b
 // With a table (`Beam` = PdeBeamTable) key j < p of row b is read from the cache row anc[b][j] instead of b; an
 // entry that names no row of the cache reads row b.  Row p is still written to row b, and everything after the
 // loads is the same code, so the output equals the plain kernel's on a cache gathered through the table bit for bit.
+// With sibling rows (`Beam` = PdeSpecRows, q rows per group) b is the physical row r: the cache has B / q rows and row
+// r uses row r / q of it; with P the position of the group's first row, key P <= j < p comes from the c_attn row of
+// sibling (r / q) * q + (j - P), which is a row below r (a state that says otherwise reads the cache instead), and row
+// p goes to the group's cache row.  Again everything after the loads is the same code.
 template <typename... Beam>
 __global__ __launch_bounds__(256) void k_dec_attn(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ cache,
                                                   const int* __restrict__ state, float* __restrict__ part, int B, int H,
                                                   int Tmax, int nch, float scale, Beam... beam) {
-  constexpr bool BEAM = sizeof...(Beam) == 1;
+  constexpr bool BEAM = dec_attn_is<PdeBeamTable, Beam...>, SPEC = dec_attn_is<PdeSpecRows, Beam...>;
   __shared__ float ps[DC_CH];
   __shared__ float ored[32][64];
   __shared__ float wred[2][4];
@@ -36,8 +49,17 @@ __global__ __launch_bounds__(256) void k_dec_attn(const bf16_t* __restrict__ qkv
   if (p < 0 || p >= Tmax || c * DC_CH > p) return;      // uniform per block
   const int C = H * 64, tid = threadIdx.x, w = tid >> 6;
   const bf16_t* row = qkv + (size_t)b * 3 * C + h * 64;  // q; + C: k; + 2C: v
-  bf16_t* Kc = cache + (size_t)bh * Tmax * 64;
-  bf16_t* Vc = Kc + (size_t)B * H * Tmax * 64;
+  int cbh = bh, CB = B;                                  // the row's (cache row, head) and the cache's rows
+  [[maybe_unused]] int g0 = 0, P0 = 0;                   // sibling rows: the group's first row and its position
+  if constexpr (SPEC) {
+    const int q = spec_rows(beam...);
+    g0 = b / q * q;
+    P0 = state[PDE_DS_POS] + state[PDE_DS_OFF + g0];
+    cbh = b / q * H + h;
+    CB = B / q;
+  }
+  bf16_t* Kc = cache + (size_t)cbh * Tmax * 64;
+  bf16_t* Vc = Kc + (size_t)CB * H * Tmax * 64;
   [[maybe_unused]] const unsigned char* anc = nullptr;
   if constexpr (BEAM) anc = beam_anc(state, b, beam...);
 
@@ -51,7 +73,11 @@ __global__ __launch_bounds__(256) void k_dec_attn(const bf16_t* __restrict__ qkv
         Ks = cache + (size_t)((a < B ? a : b) * H + h) * Tmax * 64;
       }
     }
-    const uint4* src = reinterpret_cast<const uint4*>(j1 == p ? row + C + half * 32 : Ks + (size_t)j1 * 64 + half * 32);
+    const bf16_t* ksrc = j1 == p ? row + C + half * 32 : Ks + (size_t)j1 * 64 + half * 32;
+    if constexpr (SPEC) {
+      if (j1 >= P0 && j1 < p && j1 - P0 < b - g0) ksrc = qkv + (size_t)(g0 + j1 - P0) * 3 * C + h * 64 + C + half * 32;
+    }
+    const uint4* src = reinterpret_cast<const uint4*>(ksrc);
 #pragma unroll
     for (int i = 0; i < 4; ++i) kv[i] = j1 <= p ? src[i] : make_uint4(0u, 0u, 0u, 0u);
     if (j1 == p) {
@@ -70,7 +96,11 @@ __global__ __launch_bounds__(256) void k_dec_attn(const bf16_t* __restrict__ qkv
         const int a = anc[j];
         Vs = cache + ((size_t)B * H + (size_t)((a < B ? a : b) * H + h)) * Tmax * 64;
       }
-      vv[i] = *reinterpret_cast<const uint4*>(Vs + (size_t)j * 64 + dg * 8);
+      const bf16_t* vsrc = Vs + (size_t)j * 64 + dg * 8;
+      if constexpr (SPEC) {
+        if (j >= P0 && j - P0 < b - g0) vsrc = qkv + (size_t)(g0 + j - P0) * 3 * C + h * 64 + 2 * C + dg * 8;
+      }
+      vv[i] = *reinterpret_cast<const uint4*>(vsrc);
     } else if (j == p) {
       vv[i] = *reinterpret_cast<const uint4*>(row + 2 * C + dg * 8);
       *reinterpret_cast<uint4*>(Vc + (size_t)p * 64 + dg * 8) = vv[i];

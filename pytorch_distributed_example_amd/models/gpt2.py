@@ -202,16 +202,19 @@ class Block(tnn.Module):
         x, h = T.add_layer_norm_residual(x, a, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps)
         return x, self.mlp(h), qkv
 
-    def decode_deferred(self, x, delta, cache, state, beam_table=None):
+    def decode_deferred(self, x, delta, cache, state, beam_table=None, spec=None):
         """One-token ``forward_deferred`` over the decode kernels: ``x`` / ``delta`` are ``[B, C]``, the
         new K and V are appended to ``cache`` at the position held by ``state``.  ``beam_table`` (a beam search's
-        ancestor table) makes the attention read the earlier positions through it."""
+        ancestor table) makes the attention read the earlier positions through it; ``spec`` (rows per group of a
+        speculative generation) selects the attention over sibling rows that share a cache row."""
         if delta is None:
             x, h = T.layer_norm_residual(x, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
         else:
             x, h = T.add_layer_norm_residual(x, delta, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
         qkv = D.skinny_linear(h, self.attn.c_attn.weight, self.attn.c_attn.bias)
-        if beam_table is None:
+        if spec is not None:
+            a = D.decode_attention(qkv, cache, self.layer_idx, state, spec=spec)
+        elif beam_table is None:
             a = D.decode_attention(qkv, cache, self.layer_idx, state)
         else:
             a = D.decode_attention(qkv, cache, self.layer_idx, state, beam_table=beam_table)
@@ -356,7 +359,7 @@ class GPT(tnn.Module):
                  pad_token_id=0, _after_prefill=None, repetition_penalty=1.0, frequency_penalty=0.0,
                  presence_penalty=0.0, logit_bias=None, suppress_tokens=None, min_new_tokens=0,
                  no_repeat_ngram_size=0, bad_words_ids=None, stop_sequences=None, num_beams=1, length_penalty=1.0,
-                 return_beams=False, _beam_trace=None):
+                 return_beams=False, _beam_trace=None, num_draft_tokens=0, draft_ngram=3, spec_stats=None):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` ``[B, T0]`` (``T0 >= 1``).
 
         Returns ``[B, T0 + max_new_tokens]`` int64, and with ``return_logits`` also the logits every token
@@ -417,6 +420,22 @@ class GPT(tnn.Module):
         device, so the step still replays as one graph.  With ``num_beams=1`` nothing changes and nothing is
         allocated.
 
+        ``num_draft_tokens = K >= 1`` (with ``temperature=0``) is prompt-lookup speculative decoding, defined in
+        ``ops/decode.py``: every decode step carries, beside each prompt's last token, ``K`` guessed continuations
+        found by matching the last ``draft_ngram`` (default 3, at most 8; then shorter) tokens against the prompt's
+        own history, verifies them all at once and commits the longest correct prefix plus one token.  The tokens
+        are exactly those of the plain greedy call, in fewer model steps where the text repeats itself;
+        ``return_logits`` returns the same logits bit for bit up to and including a row's finishing
+        ``eos_token_id``, and zeros in the slots after it (the one difference: a plain generation keeps recording
+        there).  ``spec_stats`` (a dict) receives ``model_steps`` (decode steps after the prefill; a plain generation
+        takes ``max_new_tokens - 1``) and ``accepted`` (int64 ``[B]``, drafts accepted per prompt).  ``prompt_lens``
+        and ``eos_token_id`` work with it; any other sampling keyword, processor, constraint or ``num_beams > 1``
+        is a ``ValueError``.  On the GPU ``B * (K + 1) <= 16`` (``NotImplementedError`` beyond); drafting, verifying
+        and advancing are kernels, the KV cache keeps ``B`` rows (the ``K + 1`` rows of a prompt share one), the step
+        replays as one graph and the host reads one "all finished" word every fourth replay.  On the CPU the plain
+        greedy loop runs -- the output is the same by definition -- and ``spec_stats`` is the replay of
+        ``spec_trace_reference``.  With ``num_draft_tokens=0`` nothing changes and nothing is allocated.
+
         ``T0 + max_new_tokens`` (``max(prompt_lens) + max_new_tokens`` for a ragged batch) must not exceed
         ``block_size`` (learned absolute positions: no sliding window)."""
         cfg = self.config
@@ -433,6 +452,21 @@ class GPT(tnn.Module):
         beam = D.BeamConfig(num_beams, length_penalty, who="generate")
         if return_beams and not beam.active:
             raise ValueError("generate: return_beams needs num_beams > 1")
+        spec = D.SpecConfig(num_draft_tokens, draft_ngram, who="generate")
+        if spec.active:
+            given = {"temperature != 0": temperature != 0, "top_k": top_k is not None, "top_p": top_p is not None,
+                     "repetition_penalty": repetition_penalty != 1.0, "frequency_penalty": frequency_penalty != 0.0,
+                     "presence_penalty": presence_penalty != 0.0, "logit_bias": logit_bias is not None,
+                     "suppress_tokens": suppress_tokens is not None, "min_new_tokens": min_new_tokens != 0,
+                     "no_repeat_ngram_size": no_repeat_ngram_size != 0, "bad_words_ids": bad_words_ids is not None,
+                     "stop_sequences": stop_sequences is not None, "num_beams > 1": beam.active}
+            off = [name for name, on in given.items() if on]
+            if off:
+                raise ValueError(f"generate: num_draft_tokens > 0 does not combine with {', '.join(off)} (speculative "
+                                 "decoding is greedy, temperature=0, and takes no processors or constraints)")
+            spec = D.SpecConfig(num_draft_tokens, draft_ngram, eos_token_id, who="generate")
+            return self._generate_spec(idx.to(dev).long(), max_new_tokens, spec, prompt_lens, int(pad_token_id),
+                                       return_logits, use_graph, _after_prefill, spec_stats)
         if beam.active:
             beam = D.BeamConfig(num_beams, length_penalty, eos_token_id, who="generate")
             given = dict(temperature=temperature != 1.0, top_k=top_k is not None, top_p=top_p is not None,
@@ -560,6 +594,46 @@ class GPT(tnn.Module):
                   finished=bb.state.finished[:R])
         return out, scores, bb.logits_out, tr
 
+    # replays between two host reads of the "all groups finished" word.  A read drains the queue, about one launch
+    # gap per read against four steps of ~0.55 ms; waiting costs at most three steps on parked rows after the end.
+    SPEC_POLL = 4
+
+    def _generate_spec(self, idx, n_new, spec, lens, pad, return_logits, use_graph, _after_prefill, stats):
+        """``generate`` with ``num_draft_tokens > 0`` on either device: on the CPU the plain greedy loop, with the
+        statistics replayed from its output; on the GPU the speculative ``DecodeSession``."""
+        was_training = self.training
+        self.eval()
+        self._generating = True
+        try:
+            with torch.no_grad():
+                if not idx.is_cuda:
+                    config = D.SamplerConfig(0.0, eos_token_id=spec.eos_token_id, who="generate")
+                    res = self._generate_cpu(idx, n_new, config, DeviceRNG(0, device=idx.device), lens, pad,
+                                             return_logits)
+                    if stats is not None:
+                        out = res[0] if return_logits else res
+                        ln = D._int_list(lens) if lens is not None else [idx.shape[1]] * idx.shape[0]
+                        steps, acc = D.spec_trace_reference(out, ln, n_new, spec.num_draft_tokens, spec.draft_ngram,
+                                                            spec.eos_token_id)
+                        stats.update(model_steps=steps, accepted=acc.sum(0))
+                    return res
+                ses = DecodeSession(self, idx, n_new, return_logits=return_logits, prompt_lens=lens, pad_token_id=pad,
+                                    spec=spec)
+                if _after_prefill is not None:
+                    _after_prefill(ses.cache)
+                if n_new > 1:
+                    run = ses.capture().replay if use_graph else ses.step
+                    for i in range(n_new - 1):          # a step yields at least one token per unfinished group
+                        run()
+                        if i % self.SPEC_POLL == self.SPEC_POLL - 1 and int(ses.spec.done.item()):
+                            break
+                if stats is not None:
+                    stats.update(ses.spec.stats())
+                return (ses.out, ses.logits_out) if return_logits else ses.out
+        finally:
+            self._generating = False
+            self.train(was_training)
+
     def _generate_cpu(self, idx, n_new, config, generator, lens, pad, return_logits):
         """One right-padded forward per token; row ``b``'s logits are row ``len_b + s - 1`` of it (causal:
         independent of what follows), gathered into ``[B, V]`` for one sampler call per step, so the
@@ -661,19 +735,34 @@ class DecodeSession:
     ``beam`` (an ``ops.BeamConfig`` with ``num_beams = K > 1``) makes it a beam search over ``B * K <= 16`` physical rows:
     the prefill still runs ``B`` rows and stores each prompt's K and V once, ``buffers`` is an ``ops.BeamBuffers`` (also
     ``beam``; ``None`` otherwise), every step's attention reads the cache through its ancestor table and the beam
-    selection takes the sampler's place.  ``beam.finalize()`` ranks the hypotheses after the last step."""
+    selection takes the sampler's place.  ``beam.finalize()`` ranks the hypotheses after the last step.
+
+    ``spec`` (an ``ops.SpecConfig`` with ``num_draft_tokens = K > 0``) makes it a speculative greedy generation over
+    ``B * (K + 1) <= 16`` physical rows: the prefill still runs ``B`` rows and fills a cache of ``B`` rows and
+    ``T0 + n_new + K`` positions (a draft row may sit up to ``K`` positions past the last token), ``buffers`` is an
+    ``ops.SpecBuffers`` (also ``spec``; ``None`` otherwise), the verify launch takes the sampler's place -- after the
+    prefill it emits the first token and drafts the first step's rows -- and every step's attention is the one over
+    sibling rows.  A step yields one to ``K + 1`` tokens per unfinished prompt; ``spec.done`` says when to stop."""
 
     def __init__(self, model, idx, n_new, temperature=1.0, top_k=None, rng_state=None, eos=None,
                  return_logits=False, top_p=None, prompt_lens=None, pad_token_id=0, processors=None,
                  repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None,
                  suppress_tokens=None, min_new_tokens=0, history=None, no_repeat_ngram_size=0, bad_words_ids=None,
-                 stop_sequences=None, config=None, beam=None):
+                 stop_sequences=None, config=None, beam=None, spec=None):
         cfg, t = model.config, model.transformer
         dev = idx.device
         B = idx.shape[0]
         beam = beam if beam is not None and beam.active else None
+        spec = spec if spec is not None and spec.active else None
+        if beam is not None and spec is not None:
+            raise ValueError("generate: beam search and speculative decoding do not combine")
         K = 1 if beam is None else beam.num_beams
-        if beam is not None:
+        if spec is not None:
+            config = spec               # greedy: the sampler's settings play no part
+            if B * (spec.num_draft_tokens + 1) > D.MAX_ROWS:
+                raise NotImplementedError(f"generate: B * (num_draft_tokens + 1) <= {D.MAX_ROWS} rows on the GPU (got "
+                                          f"{B} * {spec.num_draft_tokens + 1})")
+        elif beam is not None:
             config = beam               # the sampler's settings play no part; `check` has the same signature
         elif config is None:
             if processors is None:
@@ -695,7 +784,11 @@ class DecodeSession:
                                       f"(block_size {cfg.block_size} caps it at {Tpad})")
         self.model, self.T0, self.V = model, T0, cfg.vocab_size
         # prefill: the training kernels over the padded prompt (causal: the pad never reaches positions < T0)
-        self.cache = D.KVCache(cfg, B * K, T0 + n_new, dev)
+        if spec is None:
+            self.cache = D.KVCache(cfg, B * K, T0 + n_new, dev)
+        else:
+            self.cache = D.KVCache(cfg, B, T0 + n_new + spec.num_draft_tokens, dev,
+                                   rows=B * (spec.num_draft_tokens + 1))
         idx_pad = torch.zeros(B, Tpad, device=dev, dtype=torch.int64)
         if lens is None:
             idx_pad[:, :T0] = idx
@@ -722,7 +815,15 @@ class DecodeSession:
         h = T.add_layer_norm_residual(xl, dl, t.ln_f.weight, t.ln_f.bias, t.ln_f.eps)[1]
         # state, next, out and logits_out; with processors or constraints on also counts (the prompt flags set), work,
         # bias and stop_hit, which stay None otherwise: the sampler is then called exactly as without them
-        self.beam = self._table = None
+        self.beam = self._table = self.spec = self._spec_rows = None
+        if spec is not None:
+            self.buffers = self.spec = b = D.SpecBuffers(spec, idx, lens, n_new, self.V, wte.shape[0], dev,
+                                                         cfg.block_size, pad_token_id, return_logits)
+            self._spec_rows = spec.num_draft_tokens + 1
+            self.processors = self.history = self.counts = self.work = self.bias = self.stop_hit = None
+            self.state, self.next, self.out, self.logits_out = b.state, b.next, b.out, b.logits_out
+            self._sample(D.skinny_linear(h, wte))      # the first token, and the first step's drafts
+            return
         if beam is not None:
             # the B * K rows' state, scores, lengths, ancestor table and traces; the prompt's logits go to row b * K,
             # the only one the first beam step reads
@@ -750,7 +851,10 @@ class DecodeSession:
         t = self.model.transformer
         x, delta = D.decode_embed(self.next, t.wte.weight, t.wpe.weight, self.state), None
         for blk in t.h:
-            x, delta = blk.decode_deferred(x, delta, self.cache, self.state, self._table)
+            if self._spec_rows is None:
+                x, delta = blk.decode_deferred(x, delta, self.cache, self.state, self._table)
+            else:
+                x, delta = blk.decode_deferred(x, delta, self.cache, self.state, spec=self._spec_rows)
         h = T.add_layer_norm_residual(x, delta, t.ln_f.weight, t.ln_f.bias, t.ln_f.eps)[1]
         self._sample(D.skinny_linear(h, t.wte.weight))
 

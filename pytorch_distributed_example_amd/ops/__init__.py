@@ -19,6 +19,8 @@ from .decode import (BeamBuffers, BeamConfig, beam_rank_reference, beam_step, be
 from .decode import (DecodeState, HistoryConstraints, KVCache, LogitProcessors, SampleBuffers,  # noqa: F401
                      SamplerConfig, TokenCounts, check_top_p, decode_attention, decode_embed, history_bans_reference,
                      key16_to_float, process_logits_reference, sample, sample_reference, skinny_linear)
+from .decode import (SpecBuffers, SpecConfig, draft_reference, spec_accept_reference, spec_step,  # noqa: F401
+                     spec_trace_reference)
 from . import fp8  # noqa: F401
 from .fp8 import (Fp8Tensor, MxTensor, linear_fp8, linear_mx, mlp_fp8, mlp_mx, quantize_mx_reference,  # noqa: F401
                   quantize_reference)

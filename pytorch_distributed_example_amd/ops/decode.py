@@ -98,6 +98,35 @@ position's K and V of the hypothesis living in row ``r`` -- that ``decode_attent
 the beam step rewrites into its other half (``PdeBeamTable`` in ``pde_decode.h``); the prompt's K and V are stored
 once per prompt (``cache_fill(num_beams=)``).
 
+Speculative decoding (``SpecConfig``; ``spec_step`` on the GPU, ``draft_reference`` / ``spec_accept_reference`` /
+``spec_trace_reference`` in plain Python).  Greedy only.  ``K = num_draft_tokens >= 1``, ``q = K + 1``; prompt ``b`` owns
+the physical rows ``r = b * q + i`` of the ``R = B * q <= 16`` rows of a decode step, ``n_b`` is the number of tokens it
+has generated and its history is ``h[0 .. L-1] = out[b, 0 : L]``, ``L = len_b + n_b``.  The prefill emits the first
+token.  A step of an unfinished group:
+
+* row 0 carries ``h[L-1]`` at position ``L - 1``, row ``i >= 1`` draft ``d_i`` at position ``L - 1 + i``;
+* ``g_i`` is the lowest index attaining the maximum of ``logits[r_i, :V]``;
+* ``a`` is the largest value in ``0 .. K`` with ``d_i == g_{i-1}`` for all ``1 <= i <= a``; the group emits
+  ``g_0 .. g_a``, cut to the remaining budget ``max_new_tokens - n_b`` and after the first ``eos_token_id`` among them
+  (that token included).  The emitted tokens minus one are the step's accepted drafts;
+* a group that emitted eos is finished and the rest of its ``max_new_tokens`` slots are filled with eos at once; a
+  group whose budget is used up is finished too.  A finished group takes no further part.
+
+The next drafts are prompt lookup over the new history ``h`` of length ``L``: for ``m = draft_ngram, .., 1`` (default
+3, at most 8) take the first ``m <= L - 1`` for which some ``j`` with ``m - 1 <= j <= L - 2`` has
+``h[j-m+1 .. j] == h[L-m .. L-1]``, and of those ``j`` the largest; with ``period = L - 1 - j`` the drafts are
+``d_i = h[j + 1 + ((i - 1) mod period)]`` -- the history read as continuing periodically.  Without a match at any
+``m``, ``d_i = h[L-1]``.  Drafts only steer how many tokens a step yields, never which: the decode path's arithmetic
+is row-independent, so ``g_i`` of an accepted row has exactly the bits a plain step computes, and the generation
+returns the tokens of the plain greedy one, and with ``return_logits`` the same logits bit for bit for every slot
+up to and including a row's finishing eos (the slots after it stay zero, where a plain generation keeps recording).
+
+Idle rows -- every row of a finished group, and draft row ``i`` of a live one once ``i`` exceeds the remaining budget
+minus one or its position would leave the model's ``block_size`` -- are parked on row 0's position and token: they
+recompute row 0 and are never accepted.  The KV cache holds ``B`` rows, not ``B * q``: the rows of a group read the
+committed prefix from the group's cache row and each other's new keys from the step's own c_attn output
+(``decode_attention(spec=q)``).
+
 GPU tensors always run the framework kernels; an unsupported shape raises ``NotImplementedError``.
 """
 from __future__ import annotations
@@ -233,15 +262,18 @@ def skinny_linear(x, w, b=None, gelu: bool = False):
 
 # --------------------------------------------------------------------------------------- KV cache
 class KVCache:
-    """Keys and values of every layer: ``data[n_layer, 2, B, H, max_len, 64]`` bf16 (head dim 64 only)."""
+    """Keys and values of every layer: ``data[n_layer, 2, B, H, max_len, 64]`` bf16 (head dim 64 only).  ``rows``
+    (default ``batch``) is how many query rows a decode step brings: more than ``batch`` when the rows of a group
+    share one cache row (``decode_attention(spec=)``); it sizes the attention's scratch."""
 
-    def __init__(self, cfg, batch: int, max_len: int, device=None, dtype=_BF16):
+    def __init__(self, cfg, batch: int, max_len: int, device=None, dtype=_BF16, rows=None):
         if cfg.n_embd % cfg.n_head or cfg.n_embd // cfg.n_head != 64:
             raise NotImplementedError("KVCache: head_dim 64")
         if batch < 1 or max_len < 1:
             raise ValueError("KVCache: batch >= 1 and max_len >= 1")
         self.n_layer, self.n_head, self.batch, self.max_len = cfg.n_layer, cfg.n_head, int(batch), int(max_len)
         self.device = torch.device("cpu" if device is None else device)
+        self.rows = self.batch if rows is None else int(rows)
         self.data = torch.zeros(cfg.n_layer, 2, batch, cfg.n_head, max_len, 64, device=self.device, dtype=dtype)
         self._part = None
 
@@ -252,7 +284,7 @@ class KVCache:
         """fp32 scratch of the decode attention: one {max, sum, 64 outputs} per (b, h, key chunk)."""
         if self._part is None:
             ch = kernels().decode_attn_chunk()
-            n = self.batch * self.n_head * ((self.max_len + ch - 1) // ch) * 66
+            n = self.rows * self.n_head * ((self.max_len + ch - 1) // ch) * 66
             self._part = torch.empty(n, device=self.device, dtype=torch.float32)
         return self._part
 
@@ -282,7 +314,7 @@ def cache_fill(qkv, cache: KVCache, layer: int, T0: int, num_beams: int = 1):
         cache.data[layer, s, ::K, :, :T0] = kv
 
 
-def decode_attention(qkv_row, cache: KVCache, layer: int, state: DecodeState, beam_table=None):
+def decode_attention(qkv_row, cache: KVCache, layer: int, state: DecodeState, beam_table=None, spec=None):
     """One decode step of causal attention: append the new token's K and V (from its c_attn row
     ``[B, 3C]``) at the state's position ``p`` and return ``softmax(q K[0..p]^T / 8) V[0..p]`` as
     ``[B, C]``.  Fixed 128-key chunks with fp32 partials combined in chunk order: the output for a given
@@ -293,10 +325,17 @@ def decode_attention(qkv_row, cache: KVCache, layer: int, state: DecodeState, be
     ``beam_table`` (uint8 ``[2, 16, stride >= max_len]``, see ``beam_table()``) is a beam search's ancestor table:
     key and value ``j < p_b`` of row ``b`` are read from cache row ``table[step & 1, b, j]``, with ``step`` the state's;
     position ``p_b`` is still appended to row ``b`` itself.  The arithmetic is the same, so the output is
-    bit-identical to the call without a table on a cache gathered through it."""
+    bit-identical to the call without a table on a cache gathered through it.
+
+    ``spec = q`` (rows per group, speculative decoding) is the attention over sibling rows: ``qkv_row`` holds
+    ``R = cache.batch * q`` rows, row ``r = b * q + i`` belongs to cache row ``b``, and with ``P_b`` the position of the
+    group's first row it attends to the cache's keys ``< P_b``, then to the new keys of its siblings ``b * q .. r - 1``
+    (positions ``P_b .. p_r - 1``, taken from their ``qkv_row`` rows, not from the cache) and to its own; every row
+    appends its K and V to cache row ``b`` at ``p_r``.  Bit-identical to the plain call on a cache holding those keys."""
     B, C3 = qkv_row.shape
     H = cache.n_head
-    if C3 != 3 * H * 64 or B != cache.batch:
+    nq = 1 if spec is None else int(spec)         # rows per group
+    if C3 != 3 * H * 64 or nq < 1 or B != cache.batch * nq or (nq > 1 and (beam_table is not None or cache.rows < B)):
         raise ValueError(f"decode_attention: qkv_row {tuple(qkv_row.shape)} does not fit the cache")
     C = C3 // 3
     scale = 1.0 / math.sqrt(64)
@@ -307,7 +346,9 @@ def decode_attention(qkv_row, cache: KVCache, layer: int, state: DecodeState, be
             raise NotImplementedError(f"decode_attention: at most {MAX_ROWS} rows on the GPU (got {B})")
         out = torch.empty(B, C, device=qkv_row.device, dtype=_BF16)
         qkv_row = qkv_row if qkv_row.is_contiguous() else qkv_row.contiguous()
-        if beam_table is None:
+        if nq > 1:
+            kernels().decode_attention_spec(qkv_row, cache.layer(layer), state.buf, cache.partials(), out, H, scale, nq)
+        elif beam_table is None:
             kernels().decode_attention(qkv_row, cache.layer(layer), state.buf, cache.partials(), out, H, scale)
         else:
             kernels().decode_attention_beam(qkv_row, cache.layer(layer), state.buf, cache.partials(), out, H, scale,
@@ -317,10 +358,11 @@ def decode_attention(qkv_row, cache: KVCache, layer: int, state: DecodeState, be
     rows = []
     anc = None if beam_table is None else beam_table[state.step() & 1].long()
     for b, p in enumerate(state.row_pos(B)):
-        cache.data[layer, 0, b, :, p] = k[b]
-        cache.data[layer, 1, b, :, p] = v[b]
+        cb = b // nq             # sibling rows in row order: row r finds its siblings' keys already appended
+        cache.data[layer, 0, cb, :, p] = k[b]
+        cache.data[layer, 1, cb, :, p] = v[b]
         if anc is None:
-            Kc, Vc = cache.data[layer, 0, b, :, :p + 1].float(), cache.data[layer, 1, b, :, :p + 1].float()
+            Kc, Vc = cache.data[layer, 0, cb, :, :p + 1].float(), cache.data[layer, 1, cb, :, :p + 1].float()
         else:       # positions < p through the table ([p, H, 64] -> [H, p, 64]), position p from the row itself
             src, t = torch.cat([anc[b, :p], torch.tensor([b])]), torch.arange(p + 1)
             Kc, Vc = (cache.data[layer, s][src, :, t].transpose(0, 1).float() for s in (0, 1))
@@ -1201,4 +1243,156 @@ def beam_step(logits, buffers: BeamBuffers):
         raise NotImplementedError("beam_step: contiguous bf16 logits [B * num_beams, Vp] with Vp % 8 == 0")
     kernels().beam_step(logits, b.V, b.K, b.state.buf, b.next, b.score, b.len, b._cand[0], b._cand[1], b.table,
                         b.max_len, b.tok, b.parent, b.score_trace, b.logits_out, b.config._eos)
+    return b.next
+
+
+# --------------------------------------------------------------------------------------- speculative decoding
+def draft_reference(history, K: int, ngram: int = 3):
+    """The drafting rule (module docstring): the ``K`` tokens that prompt lookup proposes after ``history``."""
+    h = _int_list(history)
+    L = len(h)
+    if L < 1 or K < 1 or ngram < 1:
+        raise ValueError("draft_reference: a history of >= 1 tokens, K >= 1 and ngram >= 1")
+    for m in range(min(ngram, L - 1), 0, -1):
+        for j in range(L - 2, m - 2, -1):
+            if h[j - m + 1:j + 1] == h[L - m:]:
+                period = L - 1 - j
+                return [h[j + 1 + (i - 1) % period] for i in range(1, K + 1)]
+    return [h[-1]] * K
+
+
+def spec_accept_reference(greedy, drafts, n: int, budget: int, eos=None):
+    """The acceptance rule (module docstring).  ``greedy``: ``g_0 .. g_K``; ``drafts``: ``d_1 .. d_K``; ``n`` tokens
+    generated so far of ``budget = max_new_tokens``.  Returns ``(emitted, finished)``: the tokens the step emits (at
+    least one; ``len(emitted) - 1`` drafts count as accepted) and whether the group is finished after it."""
+    g, d = _int_list(greedy), _int_list(drafts)
+    if len(g) != len(d) + 1 or not 0 <= n < budget:
+        raise ValueError("spec_accept_reference: K + 1 greedy tokens for K drafts, and 0 <= n < budget")
+    a = 0
+    while a < len(d) and d[a] == g[a]:
+        a += 1
+    emitted = g[:a + 1][:budget - n]
+    hit = eos is not None and int(eos) in emitted
+    if hit:
+        emitted = emitted[:emitted.index(int(eos)) + 1]
+    return emitted, hit or n + len(emitted) >= budget
+
+
+def spec_trace_reference(tokens, lens, n_new: int, K: int, ngram: int = 3, eos=None):
+    """Replay a finished greedy generation from its tokens alone: ``tokens`` is ``[B, >= len_b + n_new]`` (the layout
+    of ``GPT.generate``), ``lens`` the ``B`` prompt lengths.  A draft is accepted iff it equals the true continuation,
+    so the trace needs no model.  Returns ``(model_steps, accepted)``: the number of decode steps after the prefill
+    (the first token comes from the prefill) and int64 ``[model_steps, B]``, the drafts accepted by every step and
+    group, 0 where the group had finished."""
+    rows = tokens.tolist() if torch.is_tensor(tokens) else tokens
+    lens = _int_list(lens)
+    per_group = []
+    for t, ln in zip(rows, lens):
+        n, acc = 1, []
+        fin = n >= n_new or (eos is not None and t[ln] == int(eos))
+        while not fin:
+            L = ln + n
+            greedy = [t[L + i] if n + i < n_new else -1 for i in range(K + 1)]      # -1: past the end, equals no draft
+            emitted, fin = spec_accept_reference(greedy, draft_reference(t[:L], K, ngram), n, n_new, eos)
+            n += len(emitted)
+            acc.append(len(emitted) - 1)
+        per_group.append(acc)
+    steps = max(len(a) for a in per_group)
+    return steps, torch.tensor([[a[s] if s < len(a) else 0 for a in per_group] for s in range(steps)],
+                               dtype=torch.int64).reshape(steps, len(lens))
+
+
+class SpecConfig:
+    """The settings of a speculative greedy generation -- ``num_draft_tokens = K``, ``draft_ngram``, ``eos_token_id`` --
+    validated once (``ValueError``).  ``active`` is False for ``K == 0``: the generation then runs as without it."""
+
+    MAX_NGRAM = 8            # PDE_HIST_MAX_NGRAM
+
+    def __init__(self, num_draft_tokens: int = 0, draft_ngram: int = 3, eos_token_id=None, who: str = "speculative"):
+        for name, v, lo in (("num_draft_tokens", num_draft_tokens, 0), ("draft_ngram", draft_ngram, 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+                raise ValueError(f"{who}: {name} must be an integer >= {lo} (got {v!r})")
+        if draft_ngram > self.MAX_NGRAM:
+            raise ValueError(f"{who}: draft_ngram must be at most {self.MAX_NGRAM} (got {draft_ngram})")
+        self.num_draft_tokens, self.draft_ngram = int(num_draft_tokens), int(draft_ngram)
+        self.eos_token_id = None if eos_token_id is None else _token_id(eos_token_id, f"{who}: eos_token_id")
+        self._eos = -1 if self.eos_token_id is None else self.eos_token_id
+
+    @property
+    def active(self) -> bool:
+        return self.num_draft_tokens > 0
+
+    def check(self, B: int, V: int, device=None):
+        if self.eos_token_id is not None and self.eos_token_id >= V:
+            raise ValueError("eos_token_id must be a token of the vocabulary")
+        return self
+
+
+class SpecBuffers:
+    """What a GPU speculative generation of ``n_new`` tokens after the prompts ``idx`` (``[B, Tin]``; ``lens`` as for
+    ``SampleBuffers``) keeps between its steps, all on the device, for the ``R = B * (K + 1)`` physical rows: the
+    ``DecodeState`` (base position 0; the offset words are the rows' positions and the verify launch rewrites them;
+    flags ``b < B`` are the groups'), ``next`` (``[R]``: committed token and drafts of every group), ``out``,
+    ``logits_out`` (``[B, n_new, V]``, zeros, with ``return_logits``), the group bases ``len`` (prompt lengths) and the
+    per-group counters ``n`` (tokens generated), ``steps`` (model steps taken part in) and ``accepted`` (drafts
+    accepted), int32 ``[B]``, and ``done``, the one word the host polls.  ``n_pos`` is the model's ``block_size``.
+    ``sample(logits)`` is one verify launch."""
+
+    def __init__(self, config: SpecConfig, idx, lens, n_new, V, Vp, device, n_pos, pad_token_id=0,
+                 return_logits=False):
+        dev = torch.device(device)
+        B, Tin = idx.shape
+        K = config.num_draft_tokens
+        R = B * (K + 1)
+        if K < 1 or R > MAX_ROWS:
+            raise NotImplementedError(f"speculative decoding: B * (num_draft_tokens + 1) <= {MAX_ROWS} rows on the GPU "
+                                      f"(got {B} * {K + 1})")
+        config.check(B, V)
+        self.config, self.V, self.B, self.K, self.n_new, self.n_pos = config, int(V), B, K, int(n_new), int(n_pos)
+        self.state = DecodeState(dev, None, pos=0, step=0)
+        self.next = torch.zeros(R, device=dev, dtype=torch.int64)
+        self.out = _prompt_out(idx, lens, n_new, pad_token_id, dev)
+        self.logits_out = torch.zeros(B, n_new, self.V, device=dev, dtype=_BF16) if return_logits else None
+        self.len = torch.tensor(lens or [Tin] * B, device=dev, dtype=torch.int32)
+        self.n, self.steps, self.accepted = (torch.zeros(B, device=dev, dtype=torch.int32) for _ in range(3))
+        self.done = torch.zeros(1, device=dev, dtype=torch.int32)
+        self._arg = torch.zeros(R, device=dev, dtype=torch.int32)
+
+    def sample(self, logits):
+        return spec_step(logits, self)
+
+    def stats(self):
+        """``model_steps`` (int) and ``accepted`` (int64 ``[B]``, CPU): a host read."""
+        return dict(model_steps=int(self.steps.max().item()), accepted=self.accepted.long().cpu())
+
+    def _dirty(self):
+        return [self.state.buf, self.next, self.n, self.steps, self.accepted, self.done]
+
+    def snapshot(self):
+        """Copies of what a step changes besides the output slots it fills: state (flags, positions), ``next``, the
+        counters and ``done``."""
+        return [t.clone() for t in self._dirty()]
+
+    def restore(self, saved):
+        for t, s in zip(self._dirty(), saved):
+            t.copy_(s)
+
+
+def spec_step(logits, buffers: SpecBuffers):
+    """One verify launch on the device (definition in the module docstring; ``spec_accept_reference`` and
+    ``draft_reference`` are its twins).  ``logits`` holds ``B * (K + 1)`` rows -- a decode step's -- or ``B`` rows, the
+    prefill's: then one token per group is emitted and no model step is counted.  A block per row finds the greedy
+    token, a block per group accepts, emits to ``out`` (and ``logits_out``), updates the counters and the flags,
+    drafts the next step's rows into ``next`` and sets their positions, and a one-thread tail sets ``done``.  Returns
+    ``next``."""
+    b = buffers
+    if not logits.is_cuda:
+        raise NotImplementedError("spec_step: the device step runs on the GPU; the CPU definition is "
+                                  "spec_accept_reference / draft_reference")
+    if logits.dim() != 2 or logits.dtype != _BF16 or logits.shape[1] % 8 or not logits.is_contiguous() \
+            or logits.shape[0] not in (b.B, b.B * (b.K + 1)):
+        raise NotImplementedError("spec_step: contiguous bf16 logits [B or B * (num_draft_tokens + 1), Vp] with "
+                                  "Vp % 8 == 0")
+    kernels().spec_step(logits, b.V, b.K, b.state.buf, b.next, b.out, b.logits_out, b.len, b.n, b.steps, b.accepted,
+                        b._arg, b.done, b.n_new, b.n_pos, b.config.draft_ngram, b.config._eos)
     return b.next

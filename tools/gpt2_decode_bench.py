@@ -30,10 +30,15 @@ plain row runs ``R`` sampled sequences and the beam row ``R / K`` prompts with `
 rows through the same step, with the table-indirect attention and the beam selection in place of the plain attention
 and the sampler -- and under ``--sampler-reps`` the beam step's three launches alone, on ``randn * 3`` logits and on rows whose logits
 are all equal (every candidate a tie at the threshold: the selection's worst case).
+``--speculative K`` adds two rows per batch size ``B`` (``B * (K + 1) <= 16``) with prompt-lookup speculative decoding
+against the plain greedy generation of the same prompts, alternating in one process: ``--window`` tokens after a
+repetitive prompt (a 16-token pattern repeated) and after uniformly random tokens, each timed on the host around the
+replays, the polls of the "all finished" word included -- ms per replay, tokens per model step and tokens per second --
+and under ``--sampler-reps`` the verify launch alone beside the greedy sampler launch.
 
     python tools/gpt2_decode_bench.py [--context 512] [--window 64] [--rounds 5] [--batch-sizes 1 16]
                                       [--top-k 50] [--top-p P] [--ragged] [--sampler-reps N] [--penalties]
-                                      [--history] [--beams K]
+                                      [--history] [--beams K] [--speculative K]
 """
 import argparse
 import json
@@ -96,6 +101,23 @@ def bench_sampler(B, cfg, top_k, top_p, reps, dev, procs=None, hist=None, contex
     e0.record()
     for _ in range(reps):
         D.sample(logits, cfg.vocab_size, state, 1.0, top_k, next=nxt, out=out, top_p=top_p, **kw)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps
+
+
+def bench_sampler_greedy(B, cfg, reps, dev):
+    """us per greedy sampler launch on ``B`` rows: what the verify launch replaces"""
+    logits = (torch.randn(B, cfg.padded_vocab, device=dev) * 3).to(torch.bfloat16)
+    state = D.DecodeState(dev, DeviceRNG(0, device=dev).state)
+    nxt, out = torch.zeros(B, device=dev, dtype=torch.int64), torch.zeros(B, 1, device=dev, dtype=torch.int64)
+    for _ in range(10):
+        D.sample(logits, cfg.vocab_size, state, 0.0, next=nxt, out=out)
+    e0, e1 = events(1)[0]
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(reps):
+        D.sample(logits, cfg.vocab_size, state, 0.0, next=nxt, out=out)
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / reps
@@ -171,6 +193,63 @@ def bench_decode(model, idx, a, lens=None, procs=None, hist=None, beams=0):
     return per_replay, per_window, eager
 
 
+def bench_speculative(model, idx, a, K):
+    """``--window`` greedy tokens after the prompts ``idx``, plain and speculative in turn, a fresh session each time
+    (prefill and capture are not timed).  Returns the medians as a dict."""
+    n_new, poll = a.window + 1, type(model).SPEC_POLL
+    spec = D.SpecConfig(K)
+    ms = {"plain": [], "spec": []}
+    replays = stats = None
+    for r in range(a.rounds + 1):                       # round 0 is warm-up
+        for kind in ("plain", "spec"):
+            if kind == "plain":
+                ses = DecodeSession(model, idx, n_new, 0.0, None, DeviceRNG(0, device=idx.device).state)
+            else:
+                ses = DecodeSession(model, idx, n_new, spec=spec)
+            graph = ses.capture()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = 0
+            for i in range(n_new - 1):
+                graph.replay()
+                n += 1
+                if kind == "spec" and i % poll == poll - 1 and int(ses.spec.done.item()):
+                    break
+            torch.cuda.synchronize()
+            if r:
+                ms[kind].append((time.perf_counter() - t0) * 1e3)
+            if kind == "spec":
+                replays, stats = n, ses.spec.stats()
+    B, tokens = idx.shape[0], a.window                  # per prompt, after the prefill's token
+    plain, sp = statistics.median(ms["plain"]), statistics.median(ms["spec"])
+    return {"num_draft_tokens": K, "prompts": B, "rows": B * (K + 1),
+            "plain_ms_per_step": round(plain / tokens, 4), "plain_tokens_per_s": round(B * tokens / (plain * 1e-3), 1),
+            "spec_ms_per_replay": round(sp / replays, 4), "replays": replays, "model_steps": stats["model_steps"],
+            "tokens_per_model_step": round(tokens / max(stats["model_steps"], 1), 3),
+            "accepted": stats["accepted"].tolist(), "spec_tokens_per_s": round(B * tokens / (sp * 1e-3), 1),
+            "speedup": round(plain / sp, 3)}
+
+
+def bench_verify(B, K, cfg, reps, dev, context=512):
+    """us per verify launch (argmax, group stage, tail) on a history of ``context`` tokens, ``reps`` calls between one
+    event pair; the counters are put back before every call so that no group finishes"""
+    logits = (torch.randn(B * (K + 1), cfg.padded_vocab, device=dev) * 3).to(torch.bfloat16)
+    idx = torch.randint(0, cfg.vocab_size, (B, context), device=dev)
+    budget = (reps + 12) * (K + 1)
+    sb = D.SpecBuffers(D.SpecConfig(K), idx, None, budget, cfg.vocab_size, cfg.padded_vocab, dev, context + budget)
+    sb.n.fill_(1)
+    for _ in range(10):
+        sb.sample(logits)
+    e0, e1 = events(1)[0]
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(reps):
+        sb.sample(logits)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps
+
+
 def bench_recompute(model, idx, reps):
     for _ in range(3):
         model(idx)[:, -1]
@@ -198,6 +277,7 @@ def main():
     ap.add_argument("--penalties", action="store_true", help="a second row per batch size with the logit processors on")
     ap.add_argument("--history", action="store_true", help="a further row with the history constraints on")
     ap.add_argument("--beams", type=int, default=0, help="a further row with beam search: batch size / K prompts x K beams")
+    ap.add_argument("--speculative", type=int, default=0, help="two further rows: speculative decoding with K drafts")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("gpt2_decode_bench: needs a GPU (no CPU fallback: a CPU time says nothing about the kernels)")
@@ -255,6 +335,21 @@ def main():
                     "bytes_per_token": {"weights": weight_bytes, "kv": int(kv_bytes)},
                     "achieved_bytes_per_s": round(bps, 1),
                     "share_of_6.29TBps": round(bps / HBM_BYTES_PER_S, 4), **extra}), flush=True)
+            if a.speculative:
+                K = a.speculative
+                if K < 1 or B * (K + 1) > D.MAX_ROWS:
+                    sys.exit(f"gpt2_decode_bench: --speculative {K} needs B * (K + 1) <= {D.MAX_ROWS} (got B = {B})")
+                g = torch.Generator(dev).manual_seed(100 + B)
+                pattern = torch.randint(0, cfg.vocab_size, (B, 16), device=dev, generator=g)
+                prompts = {"repetitive": pattern.repeat(1, a.context // 16 + 1)[:, :a.context].contiguous(), "random": idx}
+                for name, pr in prompts.items():
+                    row = {"metric": "gpt2_small_speculative_decode", "batch_size": B, "context": a.context,
+                           "window": a.window, "rounds": a.rounds, "prompt": name, **bench_speculative(model, pr, a, K)}
+                    if a.sampler_reps > 0:
+                        row["verify_us_per_launch"] = round(bench_verify(B, K, cfg, a.sampler_reps, dev, a.context), 2)
+                        row["greedy_sampler_us_per_launch"] = round(
+                            bench_sampler_greedy(B * (K + 1), cfg, a.sampler_reps, dev), 2)
+                    print(json.dumps(row), flush=True)
 
 if __name__ == "__main__":
     main()
