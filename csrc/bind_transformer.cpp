@@ -2,6 +2,7 @@
 // Every entry validates device / dtype / contiguity / shape before launching on the current stream.
 #include "pde_bind.h"
 #include "pde_kernels.h"
+#include "pde_lmhead.h"
 #include "pde_loss.h"
 #include "pde_mxfp8.h"
 
@@ -176,6 +177,54 @@ void xent_bf16(const at::Tensor& logits, const at::Tensor& tgt, int64_t V, doubl
   hip_check(pde_xent_bf16(logits.data_ptr(), ptr<int64_t>(tgt), (int)N, (int)Vp, (int)V, (float)scale,
                           ptr<float>(loss_rows), write_grad, sd, smooth ? &sm : nullptr, cur_stream()),
             "xent_bf16");
+}
+
+// The LM-head loss without logits (pde_lmhead.h): per-row lse / xt / sx (each optional, fp32 [N]) and the loss rows
+// of lm_head_loss (optional, fp32 [N]) straight from h [N, C] and w [Vp, C]; the only allocation is the partials
+// workspace [S, N, 4].  Returns S.
+int64_t lm_head_stats(const at::Tensor& h, const at::Tensor& w, const at::Tensor& tgt, int64_t V, const OptT& lse,
+                      const OptT& xt, const OptT& sx, const OptT& rows, double label_smoothing, double z_loss,
+                      const OptT& loss_weights) {
+  check_cuda(h, "h", BF16);
+  check_cuda(w, "w", BF16);
+  TORCH_CHECK(h.dim() == 2 && w.dim() == 2 && h.size(1) == w.size(1), "lm_head_stats: h must be [N, C], w [Vp, C]");
+  const int64_t N = h.size(0), C = h.size(1), Vp = w.size(0);
+  TORCH_CHECK(N >= 1, "lm_head_stats: needs at least one row");
+  TORCH_CHECK(C >= 64 && C % 64 == 0, "lm_head_stats: C must be a multiple of 64, got ", C);
+  TORCH_CHECK(Vp % 8 == 0, "lm_head_stats: the padded vocabulary must be a multiple of 8, got ", Vp);
+  TORCH_CHECK(V >= 1 && V <= Vp, "lm_head_stats: needs 1 <= V <= Vp, got V = ", V, ", Vp = ", Vp);
+  TORCH_CHECK(N <= INT32_MAX && Vp <= INT32_MAX && N * C * 2 < (int64_t(1) << 31) && Vp * C * 2 < (int64_t(1) << 31),
+              "lm_head_stats: N, Vp and the byte sizes of h and w must fit 32 bits (each operand below 2 GiB)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(h.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "lm_head_stats: h and w must be 16-byte aligned");
+  check_cuda(tgt, "targets", I64, N);
+  TORCH_CHECK(tgt.numel() == N, "lm_head_stats: targets has ", tgt.numel(), " elements, h has ", N, " rows");
+  PdeLmHeadStats p{};
+  p.h = h.data_ptr();
+  p.w = w.data_ptr();
+  p.tg = ptr<int64_t>(tgt);
+  p.lse = optr<float>(lse, "lse", F32, N);
+  p.xt = optr<float>(xt, "xt", F32, N);
+  p.sx = optr<float>(sx, "sx", F32, N);
+  p.rows = optr<float>(rows, "rows", F32, N);
+  const float* wp = optr<float>(loss_weights, "loss_weights", F32, N);
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "lm_head_stats: label_smoothing must be in [0, 1), got ",
+              label_smoothing);
+  TORCH_CHECK(z_loss >= 0.0 && std::isfinite(z_loss), "lm_head_stats: z_loss must be finite and >= 0, got ", z_loss);
+  TORCH_CHECK(w.device() == h.device() && tgt.device() == h.device(), "lm_head_stats: all tensors must be on h's device");
+  for (const OptT* o : {&lse, &xt, &sx, &rows, &loss_weights})
+    TORCH_CHECK(!o->has_value() || !(*o)->defined() || (*o)->device() == h.device(),
+                "lm_head_stats: all tensors must be on h's device");
+  p.sm = PdeXentSmooth{wp, (float)(1.0 - label_smoothing), (float)(label_smoothing / (double)V), (float)z_loss};
+  p.N = (int)N;
+  p.C = (int)C;
+  p.V = (int)V;
+  p.Vp = (int)Vp;
+  p.S = pde_lm_head_slices(p.N, p.V);
+  const at::Tensor part = at::empty({p.S, N, 4}, h.options().dtype(F32));
+  p.part = ptr<float>(part);
+  hip_check(pde_lm_head_stats(p, cur_stream()), "lm_head_stats");
+  return p.S;
 }
 
 // Masked loss (pde_loss.h): eff (int64 [N]) <- the target where it counts, else -1; info (int32 [4]) <- the
@@ -473,6 +522,11 @@ void register_transformer(pybind11::module& m) {
   m.def("xent_bf16", &xent_bf16, py::arg("logits"), py::arg("tgt"), py::arg("V"), py::arg("scale"),
         py::arg("loss_rows"), py::arg("write_grad"), py::arg("scale_dev") = py::none(),
         py::arg("label_smoothing") = 0.0, py::arg("z_loss") = 0.0, py::arg("loss_weights") = py::none());
+  m.def("lm_head_stats", &lm_head_stats, py::arg("h"), py::arg("w"), py::arg("tgt"), py::arg("V"),
+        py::arg("lse") = py::none(), py::arg("xt") = py::none(), py::arg("sx") = py::none(),
+        py::arg("rows") = py::none(), py::arg("label_smoothing") = 0.0, py::arg("z_loss") = 0.0,
+        py::arg("loss_weights") = py::none());
+  m.def("lm_head_slices", [](int64_t N, int64_t V) { return (int64_t)pde_lm_head_slices((int)N, (int)V); });
   m.def("loss_targets", &loss_targets, py::arg("targets"), py::arg("eff"), py::arg("info"), py::arg("V"),
         py::arg("ignore_index") = py::none(), py::arg("loss_mask") = py::none(), py::arg("doc_end") = py::none(),
         py::arg("T") = 1, py::arg("denom") = py::none(), py::arg("sum") = false);

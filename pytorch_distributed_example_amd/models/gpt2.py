@@ -292,7 +292,7 @@ class GPT(tnn.Module):
         return self.training and (c.embd_pdrop > 0.0 or c.attn_pdrop > 0.0 or c.resid_pdrop > 0.0)
 
     def forward(self, idx, targets=None, doc_ids=None, *, ignore_index=None, loss_mask=None, mask_doc_ends=False,
-                reduction="mean", denom=None, label_smoothing=0.0, z_loss=0.0, loss_weights=None):
+                reduction="mean", denom=None, label_smoothing=0.0, z_loss=0.0, loss_weights=None, fused_loss=False):
         """Logits ``[B, T, V]``, or the mean cross-entropy against ``targets``.
 
         ``doc_ids`` (an integer ``[B, T]`` tensor on the model's device) marks packed rows: a document
@@ -317,7 +317,10 @@ class GPT(tnn.Module):
         ``loss_weights`` (a floating ``[B, T]`` tensor, one weight per target) select the smoothed and weighted
         loss defined in ``ops.transformer.lm_head_loss``.  The mean still divides by the number of valid
         targets, whatever their weights (pass the weights' sum as ``denom`` for a weighted mean).  The two
-        numbers are frozen into a captured step; the weights are device data and follow every replay."""
+        numbers are frozen into a captured step; the weights are device data and follow every replay.
+
+        ``fused_loss=True`` computes the same loss without the ``[B * T, Vp]`` logits buffer (``lm_head_loss``'s
+        ``fused``): evaluation only, ``NotImplementedError`` where a gradient is asked for."""
         if mask_doc_ends and doc_ids is None:
             raise ValueError("GPT.forward: mask_doc_ends=True needs doc_ids")
         t = self.transformer
@@ -351,7 +354,8 @@ class GPT(tnn.Module):
         return T.lm_head_loss(x, t.wte.weight, targets, self.config.vocab_size, ignore_index=ignore_index,
                               loss_mask=loss_mask, doc_bounds=bounds if mask_doc_ends else None,
                               mask_doc_ends=mask_doc_ends, reduction=reduction, denom=denom,
-                              label_smoothing=label_smoothing, z_loss=z_loss, loss_weights=loss_weights)
+                              label_smoothing=label_smoothing, z_loss=z_loss, loss_weights=loss_weights,
+                              fused=fused_loss)
 
     # ------------------------------------------------------------------------------- generation
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, seed=None, generator=None,

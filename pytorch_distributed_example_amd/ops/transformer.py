@@ -772,8 +772,55 @@ class LMHeadLossFn(torch.autograd.Function):
         return dh.reshape(ctx.hshape), dw, None, None, None, None
 
 
+def lm_head_stats(h, w, targets, V: int, *, with_sum=False):
+    """Per-row softmax statistics of ``x = h @ w[:V]^T`` without the logits: ``(lse, xt[, sx])``, fp32 in ``h``'s
+    leading shape, for ``h [..., C]``, ``w [Vp, C]`` and integer ``targets`` of ``h``'s leading shape::
+
+        lse = logsumexp_{v < V} x[v]      xt = x[target]      sx = sum_{v < V} x[v]   (with_sum)
+
+    ``xt - lse`` is the target's log-probability.  A row whose target lies outside ``[0, V)`` does not count: all its
+    outputs are exact zeros and ``h`` is not read there.  ``w[V:]`` is never read.  No gradient.
+
+    GPU: bf16 contiguous ``h`` and ``w``, ``C % 64 == 0``, ``Vp % 8 == 0``, ``1 <= V <= Vp``, each operand below
+    2 GiB; one GEMM-shaped kernel whose epilogue is an online log-sum-exp (the logits are fp32 accumulators, never
+    rounded to bf16, never stored) and one finishing kernel, both capturable, bit-reproducible.  CPU tensors compute
+    the same definition in torch."""
+    C = h.shape[-1]
+    lead = h.shape[:-1]
+    tg = targets.reshape(-1).long()
+    if not _gpu(h):
+        x = torch.matmul(h.reshape(-1, C), w.t())[:, :V].float()
+        valid = (tg >= 0) & (tg < V)
+        x = torch.where(valid[:, None], x, x.new_zeros(()))
+        zero = x.new_zeros(())
+        out = [torch.where(valid, torch.logsumexp(x, 1), zero),
+               torch.where(valid, x.gather(1, tg.clamp(0, V - 1)[:, None])[:, 0], zero)]
+        if with_sum:
+            out.append(x.sum(1))
+        return tuple(o.view(lead) for o in out)
+    h2 = _c(h.detach().reshape(-1, C))
+    out = [torch.empty(h2.shape[0], device=h.device, dtype=torch.float32) for _ in range(3 if with_sum else 2)]
+    kernels().lm_head_stats(h2, w.detach(), _c(tg), V, lse=out[0], xt=out[1], sx=out[2] if with_sum else None)
+    return tuple(o.view(lead) for o in out)
+
+
+def _lm_head_fused(h, w, tg, V, spec, inv):
+    """``lm_head_loss`` without logits (``fused=True``): the loss rows straight from ``lm_head_stats``' kernels, then
+    the ``sum_f32`` of ``LMHeadLossFn`` under the same scale.  ``tg`` / ``inv``: as ``_lm_head_xent`` takes them."""
+    h2 = _c(h.detach().reshape(-1, h.shape[-1]))
+    N = h2.shape[0]
+    rows = torch.empty(N, device=h.device, dtype=torch.float32)
+    kernels().lm_head_stats(h2, w.detach(), _c(tg.reshape(-1).long()), V, rows=rows, label_smoothing=spec.eps,
+                            z_loss=spec.zc, loss_weights=spec.weights)
+    if spec.reduction == "none":
+        return rows.view(h.shape[:-1])
+    tot = torch.empty(1, device=h.device, dtype=torch.float32)
+    kernels().sum_f32(rows, tot, **(dict(scale=1.0 / N) if spec.plain else dict(scale=1.0, scale_dev=inv)))
+    return tot.reshape(())
+
+
 def lm_head_loss(h, w, targets, V: int, *, ignore_index=None, loss_mask=None, doc_bounds=None, mask_doc_ends=False,
-                 reduction="mean", denom=None, label_smoothing=0.0, z_loss=0.0, loss_weights=None):
+                 reduction="mean", denom=None, label_smoothing=0.0, z_loss=0.0, loss_weights=None, fused=False):
     """Cross-entropy of ``logits = h @ w[:V]^T`` against ``targets``.
 
     With every keyword at its default this is the call as it was: the mean over all ``N`` targets (on the
@@ -813,7 +860,14 @@ def lm_head_loss(h, w, targets, V: int, *, ignore_index=None, loss_mask=None, do
 
     Host path: the keywords become one ``_LossSpec``; the GPU runs ``_lm_head_xent`` (the GEMM and one ``xent_bf16``
     whose scale and smoothing keywords come from the spec), under ``LMHeadLossFn`` or, for ``"none"``, without
-    ``write_grad``; CPU tensors run ``_cpu_lm_head_loss``."""
+    ``write_grad``; CPU tensors run ``_cpu_lm_head_loss``.
+
+    ``fused=True`` (GPU; CPU tensors ignore it) computes the same loss, every flavour and reduction, without the
+    ``[N, Vp]`` logits buffer: ``lm_head_stats``' kernels keep the logits in fp32 accumulators and hand ``lse``,
+    ``x[t]`` and the row sum to the row formula above, so no logit is rounded to bf16 either.  It has no backward:
+    ``NotImplementedError`` if gradients are enabled and ``h`` or ``w`` requires one.  The limits are
+    ``lm_head_stats``'.  With every keyword at its default an out-of-range target is a zero row that counts in ``N``,
+    like a negative one."""
     spec = _loss_spec(targets, ignore_index, loss_mask, doc_bounds, mask_doc_ends, reduction, denom, label_smoothing,
                       z_loss, loss_weights)
     tg, inv = targets, None
@@ -825,6 +879,10 @@ def lm_head_loss(h, w, targets, V: int, *, ignore_index=None, loss_mask=None, do
             raise NotImplementedError("lm_head_loss: reduction='none' has no backward; call it under torch.no_grad()")
     if not _gpu(h):
         return _cpu_lm_head_loss(h, w, tg, V, spec, inv)
+    if fused:
+        if torch.is_grad_enabled() and (h.requires_grad or w.requires_grad):
+            raise NotImplementedError("lm_head_loss: fused=True has no backward; call it under torch.no_grad()")
+        return _lm_head_fused(h, w, tg, V, spec, inv)
     if reduction != "none":
         return LMHeadLossFn.apply(h, w, tg, V, spec, inv)
     # loss only (write_grad = 0): the logits stay as they are, ignored rows are not read
