@@ -59,5 +59,6 @@ void register_transformer(pybind11::module& m);
 void register_resnet(pybind11::module& m);
 void register_decode(pybind11::module& m);
 void register_fp8(pybind11::module& m);
+void register_muon(pybind11::module& m);
 
 }  // namespace pde

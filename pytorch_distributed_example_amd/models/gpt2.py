@@ -684,6 +684,13 @@ class GPT(tnn.Module):
         nodecay = [p for n, p in self.named_parameters() if p.dim() < 2]
         return [{"params": decay, "weight_decay": weight_decay}, {"params": nodecay, "weight_decay": 0.0}]
 
+    def muon_groups(self):
+        """``(block matrices, everything else)``: the ``_Linear`` weights of the blocks for ``optim.MuonMaster``;
+        wte / wpe, LayerNorm parameters and biases for ``AdamWMaster``."""
+        mats = [m.weight for blk in self.transformer.h for m in blk.modules() if isinstance(m, _Linear)]
+        ids = {id(p) for p in mats}
+        return mats, [p for p in self.parameters() if id(p) not in ids]
+
     def flops_per_token(self) -> float:
         """Training FLOPs per token (6N for the matmul weights + causal attention, PaLM appendix B)."""
         c = self.config

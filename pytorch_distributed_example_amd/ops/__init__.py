@@ -24,6 +24,8 @@ from .decode import (SpecBuffers, SpecConfig, draft_reference, spec_accept_refer
 from . import fp8  # noqa: F401
 from .fp8 import (Fp8Tensor, MxTensor, linear_fp8, linear_mx, mlp_fp8, mlp_mx, quantize_mx_reference,  # noqa: F401
                   quantize_reference)
+from . import muon  # noqa: F401
+from .muon import newton_schulz, newton_schulz_reference  # noqa: F401
 
 
 def linear(x, weight, bias=None):
